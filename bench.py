@@ -1,13 +1,19 @@
 """Headline benchmark: image-text pairs/s of the MS-CLIP-S ViT-B/32 bf16 forward + contrastive step
 (BASELINE.json configs[1]: batch 512 per GPU, synthetic 224x224 images + 77-token captions, random-init weights).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one batch per GPU with inputs resident in HBM: both towers, projection +
 L2 norm, feature all-gather (RCCL, N > 1), local row/column logits blocks, symmetric cross-entropy (+ scalar
 all-reduce).  Weak scaling: the per-GPU batch is fixed.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline record.  --full adds what takes runs or passes of
+its own: the dominant kernel's roofline (HIP-event probes in the timed region, an inline-schedule probe pass, --shapes),
+rocprofv3 counter and kernel-trace child passes, and the CPU oracle baseline.  --dump-outputs DIR writes what the last timed
+step computed (rank 0) as DIR/<name>.npy; the inputs depend only on the arguments (seeded), so two builds compare output for
+output.
 """
 import argparse
 import json
@@ -190,6 +196,34 @@ def cpu_baseline(name, sd, batch=32, iters=3):
             "sample": f"{iters} x forward+loss of {batch} pairs, fp32 torch CPU oracle, {torch.get_num_threads()} threads"}
 
 
+DUMP_MAX_ROWS = 8192                                  # feature rows per tower in a dump (2 x 8192 x E fp32 stays far below 64 MB)
+DUMP_GRAD_SAMPLE = 1024                               # entries per gradient tensor in a training-step dump
+
+
+def dump_outputs(out_dir, loss, eng, B, grads=None):
+    """What the last timed step handed its caller, as float32 .npy files under out_dir: the loss, and either this rank's unit
+    image / text features of the forward step (rows 0..DUMP_MAX_ROWS-1 at larger batches) or, for --train, a fixed sample of
+    every parameter's gradient (the same indices for a given tensor size, keys in sorted order, concatenated)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([float(loss)], dtype=np.float32)}
+    if grads is None:
+        w = eng._workspace(B, B, inference=True)          # the forward step's workspace: its heads wrote fv / ft in the last step
+        arrays["image_features"] = w["fv"][:DUMP_MAX_ROWS].float().cpu().numpy()
+        arrays["text_features"] = w["ft"][:DUMP_MAX_ROWS].float().cpu().numpy()
+    else:
+        parts = []
+        for k in sorted(grads):
+            g = grads[k].detach().float().flatten()
+            if g.numel() > DUMP_GRAD_SAMPLE:
+                idx = torch.randint(0, g.numel(), (DUMP_GRAD_SAMPLE,), generator=torch.Generator().manual_seed(g.numel()))
+                g = g[idx.to(g.device)]
+            parts.append(g.cpu())
+        arrays["grad_sample"] = torch.cat(parts).numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -220,7 +254,16 @@ def main():
     ap.add_argument("--caption-tokens", type=int, default=0,
                     help="every caption has exactly this many content tokens (75 = all 77 rows live: the line that shows what the "
                          "step costs when packing removes nothing); default 0 = SURVEY s8(d)'s synthetic captions, U{4..60} content tokens")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline probes (+ --shapes), rocprofv3 counter / "
+                         "kernel-trace child passes, CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                 # a plain run: set-up, warm-up, the timed steps and the headline record only
+        args.no_probe = args.no_pmc = args.no_hbm_kernels = args.no_cpu_baseline = True
 
     from msclip_amd import comm as C, hip, synth
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -287,10 +330,14 @@ def main():
         staged["cap"] = eng.stage_captions(tok)
         return cap
 
+    last = {}                                         # the training step's gradients of the latest step (--dump-outputs)
+
     def step():
         if ts is not None:
+            last.pop("grads", None)                   # before this step allocates: no gradients held across the next step
             loss = ts.forward(img, captions())
-            ts.step(ts.backward())
+            last["grads"] = ts.backward()
+            ts.step(last["grads"])
             return loss
         return eng.forward_loss(img, captions(), gather=True)
 
@@ -351,6 +398,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     probe, probe8 = detach_probes(probe, probe8)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, eng, B, last.get("grads"))
     shipped_plan = eng.last_plan if ts is None else None      # the launch table the timed steps replayed (None: eager loop)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     per_rank = None

@@ -616,6 +616,39 @@ def test_bench_multi_rank_plumbing_on_one_gpu(gpu_device, extra):
     assert abs(rec["value"] - 16 * 2 / (rec["ms_per_step"] * 2e-3)) / rec["value"] < 1e-2      # whole-job pairs / max-rank time
 
 
+@pytest.mark.parametrize("extra", [[], ["--train", "--bn", "frozen"]])
+def test_bench_plain_run_dumps_the_last_step(gpu_device, tmp_path, extra):
+    """A plain bench.py run (no --full) prints the headline record without the --full measurements, and --dump-outputs writes
+    the last timed step's outputs as float32 .npy files: the loss of the record, and the forward step's unit features (or a
+    training step's gradient sample)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "8", "--dump-outputs", str(out)] + extra, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 8 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-2
+    assert not {"roofline", "cpu_baseline", "hbm_bound_kernels"} & set(rec)
+    files = sorted(os.listdir(out))
+    assert files == (["grad_sample.npy", "loss.npy"] if extra else ["image_features.npy", "loss.npy", "text_features.npy"])
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["loss"].shape == (1,) and abs(float(arrays["loss"][0]) - rec["loss"]) <= 1e-4
+    if not extra:
+        for k in ("image_features", "text_features"):
+            assert arrays[k].shape == (8, 512)
+            assert np.abs(np.linalg.norm(arrays[k], axis=1) - 1.0).max() <= 1e-3
+    else:
+        assert arrays["grad_sample"].ndim == 1 and np.abs(arrays["grad_sample"]).max() > 0
+
+
 def test_conv_branch_on_side_stream_is_bitwise_the_inline_schedule(gpu_device, monkeypatch):
     """The default schedule issues the parallel convolutional branch + the adapters' top-down halves on a side HIP stream
     (they depend on the image only) with one event per adapter; MSCLIP_CONV_SIDE_STREAM=0 runs them inline: same kernels,

@@ -300,10 +300,27 @@ def l16_fixture(name="l16-fp8-msclips", batch=2):
           f"logits {logits.numpy().round(3).tolist()}, taps {sorted(taps)}, GFLOP/pair image, text = {flops}")
 
 
+def oracle_xcheck_fixture(name="b32-yfcc-msclips", seed=7):
+    """Reference features on another weight seed, batch 2 images / 3 captions (tests/test_oracle_vs_reference.py checks the
+    oracle against them)."""
+    model, _ = R.build_reference_model(name)
+    sd = synth.synth_state_dict(synth.schema_of(model), seed=seed)
+    model.load_state_dict(sd, strict=True)
+    img = synth.synth_images(2, seed=11)
+    tok = synth.synth_tokens(3, seed=12)
+    with torch.no_grad():
+        fi, ft = model.encode_image(img), model.encode_text(tok)
+    np.savez_compressed(os.path.join(OUT, f"{name}.xcheck_seed{seed}.npz"), image_features=fi.float().numpy(),
+                        text_features=ft.float().numpy(), seed=np.int64(seed), image_seed=np.int64(11), token_seed=np.int64(12))
+    print(f"{name} seed {seed}: image features {tuple(fi.shape)}, text features {tuple(ft.shape)}")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
+    if "--oracle-xcheck" in sys.argv:
+        return oracle_xcheck_fixture()
     if "--prompt-features-only" in sys.argv:
         return refresh_prompt_features()
     if "--grads-b32" in sys.argv:

@@ -1,7 +1,7 @@
 # Final round-5 check at the final code: GPU suite, C2 + training bench lines, rocprofv3 kernel stats of the same commands, timelines.
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out; O=$R/gpurun_out
 timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | tail -4 > $O/r5z_pytest.txt; cat $O/r5z_pytest.txt
-python bench.py --shapes 2>$O/r5z_c2.err | tail -1 > $O/r5z_c2_line.json; cut -c1-200 $O/r5z_c2_line.json
+python bench.py --full --shapes 2>$O/r5z_c2.err | tail -1 > $O/r5z_c2_line.json; cut -c1-200 $O/r5z_c2_line.json
 : > $O/r5z_train_lines.jsonl
 for bn in frozen batch; do python bench.py --train --bn $bn --no-cpu-baseline --no-pmc --steps 15 --warmup 5 2>/dev/null | tail -1 >> $O/r5z_train_lines.jsonl; done
 python -c "

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out; O=$R/gpurun_out
 LINES=$O/r5p_bench_lines.jsonl; : > $LINES
 run_line() {  # tag, args...
   tag=$1; shift
-  python bench.py "$@" 2>$O/r5p_$tag.err | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); r['tag']='$tag'; print(json.dumps(r))" >> $LINES
+  python bench.py --full "$@" 2>$O/r5p_$tag.err | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); r['tag']='$tag'; print(json.dumps(r))" >> $LINES
   tail -1 $LINES | cut -c1-260
 }
 run_line c2_b32_b512 --shapes
