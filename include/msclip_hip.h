@@ -428,7 +428,7 @@ int msclip_quickgelu_bwd(const void* h, const void* dy, void* dh, long long n, v
 
 /* LayerNorm backward (M.py:204-219).  Row m of the op reads x[src(m)], src(m) = row_idx ? row_idx[m] : m * row_mul;
  * dy [M, C] bf16 or fp32; dx[src(m)] = (or +=) the input gradient.  part (optional) [part_blocks][2][C] receives per-block
- * partial sums of dgamma (= sum dy * xhat) and dbeta (= sum dy): fold with msclip_colsum.  C in {512, 768}.
+ * partial sums of dgamma (= sum dy * xhat) and dbeta (= sum dy): fold with msclip_colsum.  C in {512, 768, 1024}.
  * dxb + sum_part (both or neither; row_idx NULL, row_mul 1): the written dx rows also leave as bf16 dxb [M][lddxb] -- in the
  * training step the residual-stream gradient behind a LayerNorm backward is the next projection's output gradient, the operand
  * of its dgrad / wgrad GEMMs -- with their per-block column sums in sum_part [part_blocks][C] (= or, with sum_accumulate, +=
@@ -445,9 +445,10 @@ int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx, int row_mu
 int msclip_attention_lastq(const void* q, int ldqc, const void* qkv, int ldq, void* out, int ldo, int nsamples, int L, int heads,
                            const int* last_row, int row_base, void* stream);
 
-/* Backward of msclip_attention for L <= 208: dqkv [q | k | v gradients] from qkv, the forward output o and its
+/* Backward of msclip_attention for L <= 272: dqkv [q | k | v gradients] from qkv, the forward output o and its
  * gradient dout (all bf16, same layouts as the forward).  L <= 96: the whole head resident in LDS; 97-208 (the 197-token
- * grid of ViT-B/16): query axis in blocks of 32, dK / dV accumulated in registers across the blocks.
+ * grid of ViT-B/16): query axis in blocks of 32, dK / dV accumulated in registers across the blocks; 209-272 (the 257-token
+ * grid of ViT-L/14): the same with K^T read transposed out of the row-major K instead of a resident copy.
  * colsum_part (NULL: off; L <= 96 only): fp32 [nsamples][3 * heads * 64], row b = the sums over sample b's tokens of its dqkv
  * rows (fp32 values, fixed order) -- folded over the samples (msclip_colsum) they are the in_proj bias gradient, without a second
  * pass over dqkv. */

@@ -2,7 +2,7 @@
 // workgroup of 4 waves per (sample, head), all five contractions on v_mfma_f32_16x16x32_bf16.  Up to 96 tokens (the
 // 50-token image grid of ViT-B/32 and the 77-token captions) everything of the head is resident in LDS
 // (attn_bwd_kernel, described here); 97-208 tokens (the 197-token grid of ViT-B/16) run the query-blocked form further
-// down (attn_bwd_qb_kernel).
+// down (attn_bwd_qb_kernel), and 209-272 tokens (the 257-token grid of ViT-L/14) its variant without a resident K^T.
 //
 //   S  = Q K^T (q pre-scaled by the packed in_proj weight),  P = softmax(S),  O = P V            (recomputed / given)
 //   dV = P^T dO      dP = dO V^T      dS = P o (dP - delta),  delta_q = sum_d dO[q][d] O[q][d]
@@ -336,8 +336,14 @@ int launch_bwd(const void* qkv, const void* o, const void* dout, void* dqkv, int
 // ------------------------------------------------------------------------------------------------------------
 // Waves per workgroup of the query-blocked kernel: its 153 KB of LDS also mean one workgroup per CU.
 constexpr int QB_WAVES = 8;
-
-template <int NT16, bool CAUSAL>
+//
+// 208 < L <= 272 (the 257-token grid of ViT-L/14: NT16 = 17, LP = 272, LPK = 288) run the same kernel with KTR = true: the
+// resident K^T [64][LS] (37 KB) would take the footprint to 199 KB, over the CU's 160 KiB.  Instead dQ^T = K^T . dS reads its
+// K^T fragments from the row-major K with ds_read_b64_tr_b16 (ld_tr8, as attn_bwd_kernel's phase 2 does), and K gets the
+// k-step padding rows [LP, LPK) (zero) instead:
+//   K [288][72] 41.5 KB + V [272][72] 39.2 KB + Q/dO blocks 9.2 KB + their transposes 10.2 KB + P^T/dS^T [272][40] 43.5 KB
+//   + dS [32][296] 18.9 KB + delta / statistics 1.2 KB = 163 712 B of the 163 840.
+template <int NT16, bool CAUSAL, bool KTR = false>
 __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                           const bf16_t* __restrict__ dout, bf16_t* __restrict__ dqkv, int L,
                                                           int H, int ldq, int ldo) {
@@ -345,11 +351,12 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
   constexpr int QB = 32, QS = QB + 8;                                       // queries per block, [..][query] stride
   constexpr int NW = QB_WAVES, KH = NW / 2;                                 // waves; key parts of phase 1 (two query tiles x KH)
   constexpr int NA = (2 * 4 * NT16 + NW - 1) / NW;                          // dV^T / dK^T accumulator tiles per wave
+  constexpr int KR = KTR ? LPK : LP;                                        // rows of the K image
   extern __shared__ __attribute__((aligned(16))) bf16_t sm[];
-  bf16_t* K = sm;                                      // [LP][RS]
-  bf16_t* V = K + LP * RS;
-  bf16_t* KT = V + LP * RS;                            // [64][LS]
-  bf16_t* Qb = KT + 64 * LS;                           // [QB][RS]
+  bf16_t* K = sm;                                      // [KR][RS]
+  bf16_t* V = K + KR * RS;                             // [LP][RS]
+  bf16_t* KT = V + LP * RS;                            // [64][LS]   (not with KTR)
+  bf16_t* Qb = KT + (KTR ? 0 : 64 * LS);               // [QB][RS]
   bf16_t* dOb = Qb + QB * RS;
   bf16_t* QT = dOb + QB * RS;                          // [64][QS]
   bf16_t* dOT = QT + 64 * QS;
@@ -369,6 +376,18 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
   bf16_t* gb = dqkv + row0 * ldq + h * 64;
 
   // ---- resident operands: K, V rows, K^T (zero beyond L, and in the k-step padding columns)
+  if constexpr (KTR) {
+    for (int idx = tid; idx < KR * 8; idx += 64 * NW) {
+      const int r = idx >> 3, c = idx & 7;
+      uint4 k4 = make_uint4(0, 0, 0, 0), v4 = k4;
+      if (r < L) {
+        k4 = *(const uint4*)(qb + (size_t)r * ldq + H * 64 + c * 8);
+        v4 = *(const uint4*)(qb + (size_t)r * ldq + 2 * H * 64 + c * 8);
+      }
+      *(uint4*)(K + r * RS + c * 8) = k4;
+      if (r < LP) *(uint4*)(V + r * RS + c * 8) = v4;
+    }
+  } else
   for (int idx = tid; idx < LP * 8; idx += 64 * NW) {
     const int r = idx >> 3, c = idx & 7;
     uint4 k4 = make_uint4(0, 0, 0, 0), v4 = k4;
@@ -387,7 +406,8 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
   }
   if constexpr (LPK > LP) {
     constexpr int PADC = LPK - LP;
-    for (int idx = tid; idx < 64 * PADC; idx += 64 * NW) KT[(idx / PADC) * LS + LP + idx % PADC] = 0;
+    if constexpr (!KTR)
+      for (int idx = tid; idx < 64 * PADC; idx += 64 * NW) KT[(idx / PADC) * LS + LP + idx % PADC] = 0;
     for (int idx = tid; idx < QB * PADC; idx += 64 * NW) dS[(idx / PADC) * LS + LP + idx % PADC] = 0;
   }
 
@@ -531,7 +551,32 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
     }
     for (int t = wave; t < 4 * (QB / 16); t += NW) {
       const int dt = t >> 1, tq = t & 1;
-      const f32x4 a = mma(f32x4{0.f, 0.f, 0.f, 0.f}, KT + dt * 16 * LS, LS, dS + tq * 16 * LS, LS, KL{});
+      f32x4 a;
+      if constexpr (KTR) {
+        // A fragment (head-dim row dt*16 + r16, keys ks*32 + quad*8 .. + 7) transposed out of the row-major K (see attn_bwd_kernel)
+        // in batches of KC k-steps: all nine at once would hold 72 fragment registers beside the 17 dV / dK accumulators of a
+        // wave and spill (112-152 B of scratch per lane); batches of three: none
+        constexpr int KS = LPK / 32, KC = 3;
+        const char* abase = (const char*)(K + (quad * 8 + (r16 >> 2)) * RS + dt * 16 + 4 * (r16 & 3));
+        a = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k0 = 0; k0 < KS; k0 += KC) {
+          bf16x8 af[KC], bb[KC];
+#pragma unroll
+          for (int j = 0; j < KC; ++j) {
+            const int ks = k0 + j < KS ? k0 + j : KS - 1;
+            af[j] = ld_tr8(abase + ks * 32 * RS * 2, abase + (ks * 32 + 4) * RS * 2);
+            bb[j] = *(const bf16x8*)(dS + (tq * 16 + r16) * LS + ks * 32 + quad * 8);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int j = 0; j < KC; ++j)
+            if (k0 + j < KS) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j], bb[j], a, 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+        a = mma(f32x4{0.f, 0.f, 0.f, 0.f}, KT + dt * 16 * LS, LS, dS + tq * 16 * LS, LS, KL{});
+      }
       const int tok = q0 + tq * 16 + r16;
       if (tok < L) {
         uint2 u;
@@ -557,15 +602,17 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
   }
 }
 
-template <int NT16, bool CAUSAL>
+template <int NT16, bool CAUSAL, bool KTR = false>
 int launch_bwd_qb(const void* qkv, const void* o, const void* dout, void* dqkv, int nsamples, int L, int H, int ldq, int ldo,
                   hipStream_t st) {
   constexpr int LP = NT16 * 16, LPK = (LP + 31) / 32 * 32, LS = LPK + 8, QB = 32, QS = QB + 8;
-  const size_t lds = (size_t)(2 * LP * RS + 64 * LS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + (1 + QB_WAVES) * QB * 4;
+  constexpr size_t lds = KTR ? (size_t)(LPK * RS + LP * RS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + (1 + QB_WAVES) * QB * 4
+                             : (size_t)(2 * LP * RS + 64 * LS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + (1 + QB_WAVES) * QB * 4;
+  static_assert(lds <= 160 * 1024, "the query-blocked form must fit one CU's LDS");
   bool attr_ok = true;
-  MSCLIP_LDS_ATTR((&attn_bwd_qb_kernel<NT16, CAUSAL>), lds, attr_ok);
+  MSCLIP_LDS_ATTR((&attn_bwd_qb_kernel<NT16, CAUSAL, KTR>), lds, attr_ok);
   (void)attr_ok;
-  hipLaunchKernelGGL((attn_bwd_qb_kernel<NT16, CAUSAL>), dim3(nsamples * H), dim3(64 * QB_WAVES), lds, st, (const bf16_t*)qkv,
+  hipLaunchKernelGGL((attn_bwd_qb_kernel<NT16, CAUSAL, KTR>), dim3(nsamples * H), dim3(64 * QB_WAVES), lds, st, (const bf16_t*)qkv,
                      (const bf16_t*)o, (const bf16_t*)dout, (bf16_t*)dqkv, L, H, ldq, ldo);
   return msclip_launch_status();
 }
@@ -575,10 +622,12 @@ int launch_bwd_qb(const void* qkv, const void* o, const void* dout, void* dqkv, 
 extern "C" int msclip_attention_bwd(const void* qkv, const void* o, const void* dout, void* dqkv, int nsamples, int L,
                                     int heads, int ldq, int ldo, int causal, float* colsum_part, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_attention_bwd, stream, qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, causal, colsum_part);
-  if (!qkv || !o || !dout || !dqkv || nsamples <= 0 || L <= 0 || L > 208 || heads <= 0 || (ldq % 8) || (ldo % 8))
+  if (!qkv || !o || !dout || !dqkv || nsamples <= 0 || L <= 0 || L > 272 || heads <= 0 || (ldq % 8) || (ldo % 8))
     return MSCLIP_EINVAL;
   if (colsum_part && L > 96) return MSCLIP_EINVAL;      // the query-blocked form does not carry the per-sample column sums
   hipStream_t st = (hipStream_t)stream;
+  if (L > 208) return causal ? launch_bwd_qb<17, true, true>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st)
+                             : launch_bwd_qb<17, false, true>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st);
   if (L > 160) return causal ? launch_bwd_qb<13, true>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st)
                              : launch_bwd_qb<13, false>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st);
   if (L > 96) return causal ? launch_bwd_qb<10, true>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st)

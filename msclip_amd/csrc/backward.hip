@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void quickgelu_bwd_kernel(const bf16_t* __rest
 }
 
 // ---- LayerNorm backward (TF-style LN of M.py:204-219: biased variance, eps inside the sqrt, fp32 statistics).
-// One wave per row, C = 64 * V4 * 4 (768 -> V4 = 3, 512 -> 2).  x row m comes from x[src(m)], src(m) = row_idx ? row_idx[m]
+// One wave per row, C = 64 * V4 * 4 (1024 -> V4 = 4, 768 -> 3, 512 -> 2).  x row m comes from x[src(m)], src(m) = row_idx ? row_idx[m]
 // : m * row_mul (the cls / EOT gathers of the heads); dy is bf16 or fp32 [M, C]; the result goes to dx[src(m)]
 // (overwrite or +=).  dgamma / dbeta: every block accumulates its rows in registers and writes ONE partial row
 // part[blockIdx][2][C]; msclip_colsum folds the partials (deterministic).  bf16 copy of dx optional (the operand of the
@@ -941,7 +941,7 @@ extern "C" int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx,
                                     int part_blocks, int M, int C, float eps, void* dxb, int lddxb, float* sum_part,
                                     int sum_accumulate, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_layernorm_bwd, stream, x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps, dxb, lddxb, sum_part, sum_accumulate);
-  if (!x || !dy || !gamma || !dx || M <= 0 || (C != 512 && C != 768) || part_blocks < 1) return MSCLIP_EINVAL;
+  if (!x || !dy || !gamma || !dx || M <= 0 || (C != 512 && C != 768 && C != 1024) || part_blocks < 1) return MSCLIP_EINVAL;
   // bf16 copy + column sums of the written dx rows: the plain row mapping only (dxb row m = dx row m), both or neither
   if ((dxb != nullptr) != (sum_part != nullptr) || (dxb && (row_idx || row_mul != 1 || (lddxb % 4)))) return MSCLIP_EINVAL;
   int blocks = (M + 3) / 4;
@@ -959,6 +959,7 @@ extern "C" int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx,
                                       (const T*)dy, lddy, gamma, dx, lddx, accumulate, part, M, eps, (bf16_t*)dxb, lddxb, \
                                       sum_part, sum_accumulate)
   if (C == 768) { if (dy_is_f32) LNB(3, float); else LNB(3, bf16_t); }
+  else if (C == 1024) { if (dy_is_f32) LNB(4, float); else LNB(4, bf16_t); }
   else { if (dy_is_f32) LNB(2, float); else LNB(2, bf16_t); }
 #undef LNB
   return msclip_launch_status();

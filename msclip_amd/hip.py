@@ -1354,6 +1354,7 @@ def quickgelu_bwd(h, dy, dh):
 
 
 LN_PART_BLOCKS = 1024
+ATTENTION_BWD_MAX_L = 272                            # msclip_attention_bwd's longest sequence (the 257-token ViT-L/14 grid fits)
 
 
 def layernorm_bwd(x, dy, gamma, dx, M, *, row_idx=None, row_mul=1, accumulate=True, want_param_grads=True, eps=1e-12,

@@ -15,10 +15,12 @@ and one wgrad GEMM contracts over all of them; the token path of the lateral ada
 token embeddings; the AdamW step and the rank averaging (comm.GradReducer).  train_conv.py: the convolutional side
 (stem, parallel branch, adapter convolutions) with train-mode BatchNorm (bn="batch": per-GPU batch statistics, running
 statistics updated) or frozen statistics (bn="frozen").  Together: all 325 gradient tensors of both released configs.
+The patch-conv ViT-L/14 (BASELINE config C5, 257-token grid; bf16 only) has no conv side: its 406 gradient tensors are the
+token side's plus the patch weight's (_patch_wgrad), and bn is moot there (no BatchNorm layer).
 
 Parity: tests/test_gpu_train.py compares every gradient with autograd of the REAL reference
 (tests/golden/*.grads.npz in eval() mode, b32-yfcc-msclips.grads_trainbn.npz in train() mode; captured by
-tools/make_golden.py::grads_fixture).
+tools/make_golden.py::grads_fixture); the L/14 in tests/test_gpu_train_l14.py (l14-fp8-msclips.grads.npz).
 """
 
 import torch
@@ -59,6 +61,9 @@ class TrainStep:
         self.model = model
         self.eng = model.engine()
         self.dev = self.eng.dev
+        if self.eng.patch and self.eng.fp8:
+            raise NotImplementedError("TrainStep trains the patch-conv (ViT-L/14) model in bf16 only: build it with "
+                                      "MODEL.SPEC.PRECISION bf16 (fp8 training is not implemented)")
         self.lr, self.lr_share = lr, lr_share
         self.wd, self.wd_share = wd, wd_share
         self.betas, self.eps = betas, eps
@@ -79,15 +84,16 @@ class TrainStep:
         with torch.cuda.device(e.dev), torch.no_grad():
             Bi, Bt = img.shape[0], tok.shape[0]
             assert Bi == Bt, "a training step needs image-text pairs"
-            if e.Lv > 208 or e.Lt > 208:
-                raise NotImplementedError("msclip_attention_bwd covers sequences up to 208 tokens")
+            if e.Lv > hip.ATTENTION_BWD_MAX_L or e.Lt > hip.ATTENTION_BWD_MAX_L:
+                raise NotImplementedError(f"msclip_attention_bwd covers sequences up to {hip.ATTENTION_BWD_MAX_L} tokens")
             prev = getattr(self, "saved", None)
             if prev is not None:                                   # a forward that was never differentiated: release its maps
                 prev["w"].pop("held", None)
                 self.saved = None
             w = e._workspace(Bi, Bt)
-            # the conv side's maps (w["stem"], w["par"], w["pool"], S1, P0) are read again by backward(): until then the
-            # engine's inference entry points (an eval / logging call of the same shape in between) get another workspace
+            # the conv side's maps (w["stem"], w["par"], w["pool"], S1, P0) -- or the patch-conv model's patch matrix
+            # w["PATCH"] -- are read again by backward(): until then the engine's inference entry points (an eval / logging
+            # call of the same shape in between) get another workspace
             w["held"] = True
             # captions run packed like the inference path (engine.text_pack_enabled): rows behind a caption's EOT position
             # neither influence an output nor receive a gradient.  `tok` may be a batch staged ahead (engine.stage_captions).
@@ -111,7 +117,7 @@ class TrainStep:
             sv["img"] = e._check_img(img)
             e.force_unfused = True                   # layer-by-layer conv side: every map the backward reads stays in `w`
             cb = None
-            if self.bn == "batch":
+            if self.bn == "batch" and not e.patch:             # (the patch-conv model has no BatchNorm: bn is moot there)
                 if self.convbn is None:
                     self.convbn = ConvSideBatchNorm(self)
                 cb = self.convbn
@@ -124,7 +130,7 @@ class TrainStep:
             # the inference schedule (layer by layer: force_unfused keeps every map the backward reads in the workspace)
             conv_events = None
             # (same-box A/B: 89.6-90.2 -> 88.5-88.9 ms per step)
-            if (cb is None and not gradgemm._ranks_share_a_gpu() and not options.TRAIN.wgrad_sync
+            if (cb is None and not e.patch and not gradgemm._ranks_share_a_gpu() and not options.TRAIN.wgrad_sync
                     and e.lateral == sorted(e.lateral)):
                 conv_events = e._conv_branch_on_side_stream(w, Bi)
             if (cb is not None and conv_events is None and not gradgemm._ranks_share_a_gpu() and not options.TRAIN.wgrad_sync
@@ -415,7 +421,9 @@ class TrainStep:
             grads["logit_scale"] = dscale.reshape(())
 
             dX = torch.zeros(M, D, dtype=F32, device=dev)
-            if self.bn == "batch":
+            if e.patch:
+                conv = None                              # patch-conv stem: its weight gradient at the end (_patch_wgrad)
+            elif self.bn == "batch":
                 conv = self.convbn                       # holds the raw conv outputs / batch statistics of this forward
             else:
                 conv = ConvSideBackward(self)
@@ -703,12 +711,27 @@ class TrainStep:
             grads["visual.positional_embedding"] = dvpos
             grads["visual.class_embedding"] = dvpos[0].clone()
             folds.run()                                      # every deferred column sum of the transformer's backward, two launches
-            conv.stem(grads, dtok)
+            if conv is None:
+                self._patch_wgrad(grads, dtok, sv["w"]["PATCH"], Bi)
+            else:
+                conv.stem(grads, dtok)
             flush_wgrads()
             gradgemm.join(dev)                                   # the gradients queued on the lane stream
             sv["w"].pop("held", None)
             self.saved = None
             return reducer.finish(clone=clone) if reducer is not None else dict(grads)
+
+    def _patch_wgrad(self, grads, dtok, patch, Bi):
+        """visual.conv1.weight [D, 3, P, P] of the patch-conv stem (M.py:2657; kernel == stride == P, no bias): the forward was
+        X[grid rows] = PATCH . W_patch^T over msclip_patchify's matrix (columns (c, kh, kw) in the weight's memory order, zero
+        padding up to patch_k), so dW = dTok[grid rows]^T . PATCH -- the class rows skipped by the cast pass -- with the padding
+        columns dropped."""
+        e = self.eng
+        g2, D, P = e.g * e.g, e.D, e.S // e.g
+        kp = 3 * P * P
+        dgrid = hip.cast_bf16_colsum(dtok[:Bi * e.Lv], fold=False, skip_group=g2)[0]      # grid rows, one pass, no gather copy
+        grads["visual.conv1.weight"] = _wgrad_async(dgrid, patch[:Bi * g2], Bi * g2,
+                                                    post=lambda d: d[:, :kp].reshape(D, 3, P, P).contiguous())
 
     # ------------------------------------------------------------------ optimizer
     def set_epoch(self, epoch):

@@ -155,11 +155,12 @@ def zeroshot_fixture(model, name):
     print(f"{name}: zero-shot fixture top1 {top1:.2f}% on 64 generated images, W {tuple(W.shape)}")
 
 
-def grads_fixture(model, name, train_bn=False, batch=None, tag=None, full_limit=4096):
+def grads_fixture(model, name, train_bn=False, batch=None, tag=None, full_limit=4096, full_keep=None):
     """f3 (backward) fixture: autograd of the REAL reference through forward(image, text) and the symmetric CE
     0.5 * (CE(logits) + CE(logits^T)) (the loss itself is not in the reference), eval-mode BatchNorm,
     fp32, the golden batch.  Stored per parameter: mean, abs-mean, abs-max and a 64-point strided sample of the gradient (the
-    shared tensors' gradients are the SUM over both towers: one Parameter object, M.py:2808-2830), plus the loss."""
+    shared tensors' gradients are the SUM over both towers: one Parameter object, M.py:2808-2830), plus the loss.  Full copies of
+    the tensors of at most full_limit elements (for which full_keep(name), when given, holds)."""
     nb = batch or BATCH                      # train-mode BN: 16 (statistics over 4 images are ill-conditioned in any precision)
     img = synth.synth_images(nb, seed=SEED)
     tok = synth.synth_tokens(nb, seed=SEED + 1)
@@ -187,7 +188,7 @@ def grads_fixture(model, name, train_bn=False, batch=None, tag=None, full_limit=
         seen[id(p)] = k
         out["g_" + k] = summarize(p.grad)
         out["gmax_" + k] = np.float32(p.grad.abs().max().item())
-        if p.grad.numel() <= full_limit:
+        if p.grad.numel() <= full_limit and (full_keep is None or full_keep(k)):
             out["gfull_" + k] = p.grad.detach().numpy().astype(np.float32)
     if train_bn:
         after = model.state_dict()
@@ -330,6 +331,21 @@ def main():
         model, _ = build_only("b32-yfcc-msclips")
         grads_fixture(model, "b32-yfcc-msclips", batch=32, tag="_b32", full_limit=1024)
         grads_fixture(model, "b32-yfcc-msclips", train_bn=True, batch=32, tag="_b32", full_limit=1024)
+        return
+    if "--grads-l14" in sys.argv:
+        # BASELINE config C5 (ViT-L/14, patch-conv stem, 257-token grid): reference autograd in eval mode at the golden batch, the
+        # pin of TrainStep on that model (trained in bf16: the reference has no fp8 semantics).  406 gradient tensors: summaries of
+        # all, full copies of the <= 1024-element ones outside the transformer blocks and in blocks 0, 1, 11, 22, 23 of both
+        # towers (every block's would take the file past 1 MB).
+        import re
+        model, _ = build_only("l14-fp8-msclips")
+        model.eval()
+        blk = re.compile(r"resblocks\.(\d+)\.")
+
+        def keep(k):
+            m = blk.search(k)
+            return m is None or int(m.group(1)) in (0, 1, 11, 22, 23)
+        grads_fixture(model, "l14-fp8-msclips", full_limit=1024, full_keep=keep)
         return
     if "--l16" in sys.argv:
         return l16_fixture()

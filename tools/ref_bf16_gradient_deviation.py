@@ -61,6 +61,8 @@ def compare(ref, got):
     res = {}
     for c in ("token_side", "conv_side", "ln_bias"):
         v = [rows[k] for k in rows if cls(k) == c]
+        if not v:                           # (the patch-conv L/14 has no conv side)
+            continue
         res[c] = {"tensors": len(v), "sample_err_median": float(np.median([x[0] for x in v])),
                   "sample_err_worst": float(max(x[0] for x in v)), "absmean_dev_worst": float(max(x[1] for x in v)),
                   "cosine_lowest": float(min(x[2] for x in v))}
@@ -86,6 +88,17 @@ def main():
     torch.manual_seed(0)
     torch.set_num_threads(16)
     R.ensure_single_rank_group()
+    if "--l14" in sys.argv:
+        # the yardstick of tests/golden/l14-fp8-msclips.grads.npz (tools/make_golden.py --grads-l14): its own file, the B/32 and
+        # B/16 numbers above stay untouched
+        path = os.path.join(ROOT, "tests", "golden", "ref_bf16_gradient_deviation_l14.json")
+        out = {"what": ("reference gradients under torch.autocast(bfloat16) against the same reference in fp32 (CPU), metrics of "
+                        "tests/test_gpu_train.py; the batch of tools/make_golden.py --grads-l14"),
+               "model": "l14-fp8-msclips"}
+        out.update(run_model("l14-fp8-msclips", (("eval_bn_batch4", 4, False),)))
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+        return
     path = os.path.join(ROOT, "tests", "golden", "ref_bf16_gradient_deviation.json")
     only = sys.argv[1] if len(sys.argv) > 1 else None
     out = json.load(open(path)) if only and os.path.exists(path) else {}
