@@ -11,6 +11,9 @@
  * raw upper half of an IEEE fp32 (uint16).  Return value: 0 = launched,
  * MSCLIP_EINVAL (-1) = rejected arguments, MSCLIP_ELAUNCH (-2) = HIP launch
  * error.  "out_kind": 0 = bf16, 1 = fp32.
+ *
+ * Declaration style -- msclip_amd/abi.py binds Python from this text and refuses anything else: `typedef struct T {...} T;` and
+ * `int` / `const char*` prototypes over int, float, long long, void, char, the structs, `*` and `* const*`; no arrays or bit-fields.
  */
 #ifndef MSCLIP_HIP_H
 #define MSCLIP_HIP_H

@@ -1,0 +1,95 @@
+"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.
+
+The mapping rule, for prototype parameters and struct members alike:
+    int -> c_int, float -> c_float, long long -> c_longlong;
+    `T**` and `T* const*` -> POINTER(c_void_p);
+    every other pointer -> c_void_p, struct pointers included (callers pass byref(desc), a ctypes array or an address);
+    a return type is `int` -> c_int or `const char*` -> c_char_p.
+A struct member whose name is a Python keyword gets a trailing underscore (`in` -> `in_`).
+
+The reader knows the C subset that the header's comment block names and raises AbiError on anything else; it never guesses.
+"""
+import collections
+import ctypes
+import keyword
+import os
+import re
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "msclip_hip.h")
+
+Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
+
+
+class AbiError(ValueError):
+    pass
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong}
+_BASE = r"(?:const\s+)?(int|float|long long|void|char|msclip_\w+)\b"
+_DECL = re.compile(_BASE + r"\s*(\*|\*\s*\*|\*\s*const\s*\*)?\s*([A-Za-z_]\w*)")
+_PROTO = re.compile(r"(int|const\s+char\s*\*)\s*(msclip_\w+)\s*\((.*)\)", re.S)
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)(?:\s*\{([^{}]*)\}\s*|\s+)(\w+)")
+
+
+def _declarator(text, known):
+    """`const float* x` -> ("x", c_void_p).  `known`: the struct names declared so far."""
+    m = _DECL.fullmatch(text.strip())
+    if not m:
+        raise AbiError(f"cannot read the declarator {text.strip()!r}")
+    base, stars, name = m.groups()
+    if base.startswith("msclip_") and base not in known:
+        raise AbiError(f"unknown type {base!r} in {text.strip()!r}")
+    if not stars:
+        if base not in _SCALARS:
+            raise AbiError(f"{base!r} by value in {text.strip()!r}")
+        return name, _SCALARS[base]
+    return name, ctypes.c_void_p if stars == "*" else ctypes.POINTER(ctypes.c_void_p)
+
+
+def _members(body, known):
+    fields = []
+    for line in filter(None, (s.strip() for s in body.split(";"))):
+        first, *rest = line.split(",")
+        base = re.match(_BASE, first)                   # `const float *g, *b;`: the later declarators share the first one's type
+        if not base:
+            raise AbiError(f"cannot read the struct member {line!r}")
+        for d in [first] + [base.group(0) + " " + r for r in rest]:
+            name, ctype = _declarator(d, known)
+            fields.append((name + "_" * keyword.iskeyword(name), ctype))
+    return fields
+
+
+def parse(text):
+    """Header text -> Abi."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+MSCLIP_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    if len(version) != 1:
+        raise AbiError(f"expected one '#define MSCLIP_ABI_VERSION <number>', found {len(version)}")
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    structs, protos = {}, {}
+    for stmt in filter(None, (s.strip() for s in re.split(r";(?![^{}]*\})", text))):      # (a struct body's own `;` do not split)
+        struct = _STRUCT.fullmatch(stmt)
+        proto = _PROTO.fullmatch(stmt)
+        if struct:
+            tag, body, name = struct.groups()
+            if tag != name or name in structs:
+                raise AbiError(f"struct {tag!r} / typedef {name!r}: one name, declared once")
+            structs[name] = None                        # opaque (`typedef struct T T;`): only ever pointed to
+            if body is not None:
+                mirror = {"_fields_": _members(body, structs), "__doc__": f"Mirror of struct {name}."}
+                structs[name] = type(name, (ctypes.Structure,), mirror)
+        elif proto:
+            if proto.group(2) in protos:
+                raise AbiError(f"{proto.group(2)} is declared twice")
+            params = proto.group(3).strip()
+            args = [] if params == "void" else [_declarator(p, structs)[1] for p in params.split(",")]
+            protos[proto.group(2)] = (ctypes.c_int if proto.group(1) == "int" else ctypes.c_char_p, args)
+        else:
+            raise AbiError(f"cannot read the declaration {stmt[:80]!r}")
+    return Abi(int(version[0]), {k: v for k, v in structs.items() if v}, protos)
+
+
+def load(path=HEADER):
+    with open(path) as f:
+        return parse(f.read())

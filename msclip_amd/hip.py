@@ -11,32 +11,17 @@ import subprocess
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSCLIP_HIP_LIB") or os.path.join(_HERE, "csrc", "libmsclip_hip.so")   # override: kernel A/B probes only
 INT_MAX = 2 ** 31 - 1
-ABI_VERSION = 8                                          # include/msclip_hip.h MSCLIP_ABI_VERSION
-
-EXPORTS = (
-    "msclip_gemm", "msclip_gemm_f8", "msclip_layernorm_stats", "msclip_rowstat_finalize", "msclip_layernorm_f8", "msclip_quant_f8_rows", "msclip_gemm_variant", "msclip_attention", "msclip_attention_lastq", "msclip_layernorm", "msclip_layernorm_split", "msclip_embed_tokens", "msclip_fill_cls",
-    "msclip_adapter_combine_ln", "msclip_adapter_combine_ln_stats", "msclip_l2norm", "msclip_gather_rows", "msclip_stem_conv3x3s2_dual", "msclip_stem_conv3x3s2_dual_raw", "msclip_stem_conv3x3s2_dual_stats", "msclip_stem_conv3x3s2_dual_norm", "msclip_dwpool",
-    "msclip_stem_dual_conv3x3s2", "msclip_conv1x1_conv3x3s2", "msclip_convresblock48_s2", "msclip_patchify",
-    "msclip_lse_rows", "msclip_clip_loss_partial", "msclip_clip_lse_fused", "msclip_clip_loss_from_partials",
-    "msclip_transpose_bf16", "msclip_cast_bf16", "msclip_cast_bf16_colsum", "msclip_colsum", "msclip_quickgelu", "msclip_quickgelu_bwd", "msclip_layernorm_bwd",
-    "msclip_attention_bwd", "msclip_l2norm_bwd", "msclip_clip_loss_bwd_g", "msclip_embed_tokens_bwd", "msclip_adapter_sum",
-    "msclip_adapter_dx", "msclip_adamw", "msclip_adamw_multi", "msclip_im2col", "msclip_col2im", "msclip_relu_bwd", "msclip_dwpool_bwd",
-    "msclip_dwpool_wgrad", "msclip_dw3x3_wgrad", "msclip_gemm_splitk", "msclip_gemm_splitk_tn", "msclip_bn_stats", "msclip_bn_apply",
-    "msclip_bn_bwd_reduce", "msclip_bn_bwd_dx", "msclip_bn_bwd_fused", "msclip_bn_fold_bwd", "msclip_bn_finish", "msclip_bn_finish_tiled", "msclip_bn_bwd_finish",
-    "msclip_text_lengths", "msclip_embed_tokens_packed", "msclip_attention_varlen", "msclip_attention_lastq_varlen",
-    "msclip_attention_bwd_varlen", "msclip_embed_tokens_bwd_packed",
-    "msclip_qkv_attention", "msclip_qkvattn_tables", "msclip_pack_weights", "msclip_transpose_bf16_multi", "msclip_image_conv_wgrad", "msclip_colsum_multi",
-    "msclip_abi_version", "msclip_build_arch",
-    "msclip_stream_priority_range", "msclip_stream_create", "msclip_stream_destroy", "msclip_stream_create_cu_masked",
-    "msclip_plan_create", "msclip_plan_destroy", "msclip_plan_begin", "msclip_plan_bind_external", "msclip_plan_record_event",
-    "msclip_plan_wait_event", "msclip_plan_end", "msclip_plan_abort", "msclip_plan_info", "msclip_plan_op_name", "msclip_plan_run",
-    "msclip_plan_size", "msclip_plan_probe_enable", "msclip_plan_probe_disable", "msclip_plan_probe_runs", "msclip_plan_probe_elapsed",
-    "msclip_comm_unique_id", "msclip_comm_init", "msclip_comm_destroy", "msclip_comm_async_error", "msclip_allgather_feats",
-    "msclip_allreduce", "msclip_prepare_device",
-)
+_ABI = abi.load()                                        # include/msclip_hip.h, read once: the only statement of the C ABI
+ABI_VERSION = _ABI.version
+EXPORTS = tuple(_ABI.protos)
+GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor = (_ABI.structs[n] for n in (
+    "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item", "msclip_transpose_item",
+    "msclip_adamw_tensor"))
 
 
 class HipUnavailable(RuntimeError):
@@ -45,49 +30,6 @@ class HipUnavailable(RuntimeError):
 
 class HipError(RuntimeError):
     pass
-
-
-class BnBwdSide(ctypes.Structure):
-    """Mirror of struct msclip_bn_bwd_side."""
-    _fields_ = [("x", ctypes.c_void_p), ("ld", ctypes.c_int), ("mean", ctypes.c_void_p), ("rstd", ctypes.c_void_p),
-                ("gamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p), ("dgamma", ctypes.c_void_p), ("dx", ctypes.c_void_p),
-                ("lddx", ctypes.c_int), ("part", ctypes.c_void_p), ("x_bf16", ctypes.c_int)]
-
-
-class GemmDesc(ctypes.Structure):
-    """Mirror of struct msclip_gemm_desc."""
-    _fields_ = [
-        ("X", ctypes.c_void_p), ("W", ctypes.c_void_p), ("zero", ctypes.c_void_p),
-        ("out", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("resid", ctypes.c_void_p),
-        ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int),
-        ("ldx", ctypes.c_int), ("ldw", ctypes.c_int), ("ldo", ctypes.c_int), ("ldr", ctypes.c_int),
-        ("mode", ctypes.c_int),
-        ("H", ctypes.c_int), ("Wd", ctypes.c_int), ("Cin", ctypes.c_int), ("Ho", ctypes.c_int),
-        ("Wo", ctypes.c_int), ("stride", ctypes.c_int), ("pad", ctypes.c_int),
-        ("ktab", ctypes.c_void_p),
-        ("act", ctypes.c_int), ("resid_kind", ctypes.c_int), ("out_kind", ctypes.c_int),
-        ("alpha", ctypes.c_float),
-        ("rpg", ctypes.c_int), ("radd", ctypes.c_int), ("roff", ctypes.c_int), ("out2", ctypes.c_void_p), ("out_scale", ctypes.c_float), ("tile", ctypes.c_int), ("wg_cap", ctypes.c_int),
-        # LayerNorm fold: consumer (W2, bias2, csum, csum2, rowstat, seg_split) and producer (ldxb, xb, center, part)
-        ("W2", ctypes.c_void_p), ("bias2", ctypes.c_void_p), ("csum", ctypes.c_void_p), ("csum2", ctypes.c_void_p),
-        ("rowstat", ctypes.c_void_p), ("seg_split", ctypes.c_int), ("ldxb", ctypes.c_int), ("xb", ctypes.c_void_p),
-        ("center", ctypes.c_void_p), ("part", ctypes.c_void_p), ("resid2", ctypes.c_void_p),
-        ("M_dev", ctypes.c_void_p),                  # device int: the kernel runs min(M, *M_dev) rows (packed captions)
-        ("bn_mode", ctypes.c_int), ("part_rows", ctypes.c_int), ("bn_consts", ctypes.c_void_p),   # two-pass train-mode BatchNorm
-    ]
-
-
-class QkvAttnDesc(ctypes.Structure):
-    """Mirror of struct msclip_qkvattn_desc."""
-    _fields_ = [
-        ("X", ctypes.c_void_p), ("W", ctypes.c_void_p), ("zero", ctypes.c_void_p), ("out", ctypes.c_void_p),
-        ("bias", ctypes.c_void_p), ("cu", ctypes.c_void_p), ("tile_first", ctypes.c_void_p), ("rowseg", ctypes.c_void_p),
-        ("ntiles_dev", ctypes.c_void_p),
-        ("M", ctypes.c_int), ("K", ctypes.c_int), ("heads", ctypes.c_int), ("ntiles", ctypes.c_int),
-        ("ldx", ctypes.c_int), ("ldw", ctypes.c_int), ("ldo", ctypes.c_int), ("causal_from_row", ctypes.c_int),
-        ("rowstat", ctypes.c_void_p), ("csum", ctypes.c_void_p), ("W2", ctypes.c_void_p), ("bias2", ctypes.c_void_p),
-        ("csum2", ctypes.c_void_p), ("seg_split", ctypes.c_int),
-    ]
 
 
 _lib = None
@@ -108,116 +50,15 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise HipUnavailable(f"{LIB_PATH} is missing: run msclip_amd/csrc/build.sh (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.msclip_gemm.argtypes = [ctypes.POINTER(GemmDesc), vp]
-        L.msclip_gemm_splitk.argtypes = [ctypes.POINTER(GemmDesc), ci, vp]
-        L.msclip_gemm_splitk_tn.argtypes = [ctypes.POINTER(GemmDesc), ci, vp]
-        L.msclip_gemm_f8.argtypes = [ctypes.POINTER(GemmDesc), vp, vp, vp]
-        L.msclip_layernorm_f8.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, cf, vp, vp]
-        L.msclip_quant_f8_rows.argtypes = [vp, ci, vp, ci, vp, ci, ci, vp]
-        L.msclip_gemm_variant.argtypes = [ctypes.POINTER(GemmDesc)]
-        L.msclip_gemm_variant.restype = ctypes.c_char_p
-        L.msclip_attention.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_attention_lastq.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, ci, vp]
-        L.msclip_layernorm.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, ci, vp, ci, ci, ci, cf, vp]
-        L.msclip_layernorm_stats.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, ci, vp, vp, ci, ci, cf, vp, vp]
-        L.msclip_rowstat_finalize.argtypes = [vp, ci, vp, vp, ci, ci, cf, vp, vp]
-        L.msclip_layernorm_split.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, cf, vp]
-        L.msclip_embed_tokens.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.msclip_fill_cls.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_adapter_combine_ln.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]
-        L.msclip_adapter_combine_ln_stats.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, cf, vp]
-        L.msclip_l2norm.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, vp]
-        L.msclip_gather_rows.argtypes = [vp, ctypes.c_longlong, vp, ci, ci, vp, ctypes.c_longlong, ci, ci, vp]
-        L.msclip_stem_conv3x3s2_dual.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_stem_conv3x3s2_dual_raw.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, vp]
-        L.msclip_stem_conv3x3s2_dual_stats.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_stem_conv3x3s2_dual_norm.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
-        L.msclip_dwpool.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_stem_dual_conv3x3s2.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_conv1x1_conv3x3s2.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_convresblock48_s2.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
-        L.msclip_patchify.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.msclip_lse_rows.argtypes = [vp, ci, vp, ci, ci, vp]
-        L.msclip_clip_loss_partial.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, vp]
-        L.msclip_clip_lse_fused.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]
-        L.msclip_clip_loss_from_partials.argtypes = [vp, vp, vp, vp, vp, ci, ci, cf, vp, vp, vp]
-        ll = ctypes.c_longlong
-        L.msclip_transpose_bf16.argtypes = [vp, ci, vp, ci, ci, ci, ci, vp]
-        L.msclip_cast_bf16.argtypes = [vp, ci, vp, ci, ci, ci, vp]
-        L.msclip_cast_bf16_colsum.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp]
-        L.msclip_colsum.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, vp]
-        L.msclip_quickgelu.argtypes = [vp, vp, ll, vp]
-        L.msclip_quickgelu_bwd.argtypes = [vp, vp, vp, ll, vp]
-        L.msclip_layernorm_bwd.argtypes = [vp, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, ci, ci, ci, cf, vp, ci, vp, ci, vp]
-        L.msclip_attention_bwd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.msclip_l2norm_bwd.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, vp]
-        L.msclip_clip_loss_bwd_g.argtypes = [vp, ci, vp, vp, ci, cf, vp, ci, vp, ci, ci, ci, vp]
-        L.msclip_embed_tokens_bwd.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_adapter_sum.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_adapter_dx.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_adamw.argtypes = [vp, vp, vp, vp, ll, cf, cf, cf, cf, cf, ci, vp]
-        L.msclip_adamw_multi.argtypes = [ctypes.POINTER(AdamwTensor), ci, cf, cf, cf, ci, vp]
-        L.msclip_im2col.argtypes = [vp, ci, vp] + [ci] * 11 + [vp]
-        L.msclip_col2im.argtypes = [vp, ci, vp] + [ci] * 11 + [vp]
-        L.msclip_relu_bwd.argtypes = [vp, vp, vp, vp, ll, vp]
-        L.msclip_dwpool_bwd.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_dwpool_wgrad.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        L.msclip_dw3x3_wgrad.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.msclip_bn_stats.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp]
-        L.msclip_bn_apply.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.msclip_bn_bwd_reduce.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp]
-        L.msclip_bn_bwd_dx.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]
-        L.msclip_bn_finish.argtypes = [vp, ci, ci, ll, vp, vp, cf, vp, vp]
-        L.msclip_bn_finish_tiled.argtypes = [vp, ci, ci, ll, vp, vp, cf, vp, ci, vp]
-        L.msclip_bn_bwd_finish.argtypes = [vp, ci, ci, ci, vp, vp, vp]
-        L.msclip_bn_bwd_fused.argtypes = [ci, vp, ci, vp, ci, vp, ci, ctypes.POINTER(BnBwdSide), ctypes.POINTER(BnBwdSide), ci, ci, ci, ll, vp]
-        L.msclip_bn_fold_bwd.argtypes = [vp, ll, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp]
-        L.msclip_text_lengths.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]
-        L.msclip_embed_tokens_packed.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.msclip_attention_varlen.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.msclip_attention_lastq_varlen.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, ci, vp]
-        L.msclip_attention_bwd_varlen.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.msclip_embed_tokens_bwd_packed.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
-        L.msclip_qkv_attention.argtypes = [ctypes.POINTER(QkvAttnDesc), vp]
-        L.msclip_qkvattn_tables.argtypes = [vp, ci, ci, vp, vp, vp, ci, ci, vp]
-        L.msclip_pack_weights.argtypes = [vp, vp, ci, ci, vp]
-        L.msclip_transpose_bf16_multi.argtypes = [vp, vp, ci, ci, vp]
-        L.msclip_colsum_multi.argtypes = [vp, ci, vp]
-        L.msclip_image_conv_wgrad.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp]
-        pp = ctypes.POINTER(vp)
-        L.msclip_plan_create.argtypes = [pp]
-        L.msclip_plan_destroy.argtypes = [vp]
-        L.msclip_plan_begin.argtypes = [vp, pp, ci]
-        L.msclip_plan_bind_external.argtypes = [vp, vp, ll]
-        L.msclip_plan_record_event.argtypes = [vp, vp]
-        L.msclip_plan_wait_event.argtypes = [vp, vp, ci]
-        L.msclip_plan_end.argtypes = [vp]
-        L.msclip_plan_abort.argtypes = [vp]
-        L.msclip_plan_info.argtypes = [vp] + [ctypes.POINTER(ci)] * 5
-        L.msclip_plan_op_name.argtypes = [vp, ci]
-        L.msclip_plan_op_name.restype = ctypes.c_char_p
-        L.msclip_plan_run.argtypes = [vp, pp, ci, pp, ci]
-        L.msclip_plan_size.argtypes = [vp]
-        L.msclip_plan_probe_enable.argtypes = [vp, ctypes.POINTER(ci), ci, ci]
-        L.msclip_plan_probe_disable.argtypes = [vp]
-        L.msclip_plan_probe_runs.argtypes = [vp]
-        L.msclip_plan_probe_elapsed.argtypes = [vp, ci, ci, ctypes.POINTER(cf)]
-        L.msclip_stream_create_cu_masked.argtypes = [ci, ci, pp]
-        L.msclip_comm_unique_id.argtypes = [vp]
-        L.msclip_comm_init.argtypes = [ci, ci, vp, pp]
-        L.msclip_comm_destroy.argtypes = [vp]
-        L.msclip_comm_async_error.argtypes = [vp]
-        L.msclip_allgather_feats.argtypes = [vp, vp, vp, ll, ci, vp]
-        L.msclip_allreduce.argtypes = [vp, vp, vp, ll, ci, ci, vp]
-        L.msclip_abi_version.restype = ci
+        for name, (restype, argtypes) in _ABI.protos.items():             # abi.py states the C type -> ctypes rule
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_hip.h declares: rebuild "
+                                     "(bash msclip_amd/csrc/build.sh)")
+            fn.restype, fn.argtypes = restype, argtypes
         if L.msclip_abi_version() != ABI_VERSION:          # a stale build of the library (the struct layouts / entry points moved on)
             raise HipUnavailable(f"{LIB_PATH} has ABI version {L.msclip_abi_version()}, this binding needs {ABI_VERSION}: rebuild "
                                  "(bash msclip_amd/csrc/build.sh)")
-        L.msclip_build_arch.restype = ctypes.c_char_p
-        for name in EXPORTS:
-            if name not in ("msclip_build_arch", "msclip_gemm_variant", "msclip_plan_op_name"):
-                getattr(L, name).restype = ci
         _lib = L
     return _lib
 
@@ -1260,12 +1101,6 @@ def cast_bf16_colsum(x, out=None, fold=True, skip_group=0):
     return out, (colsum(part) if fold else part)
 
 
-class FoldItem(ctypes.Structure):
-    """msclip_fold_item (include/msclip_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("M", ctypes.c_int), ("N", ctypes.c_int), ("ld", ctypes.c_int),
-                ("scale_n", ctypes.c_int), ("scale", ctypes.c_float)]
-
-
 class FoldPlan:
     """Deferred column sums of one backward pass: producers leave per-block partial matrices (fp32 [M, N]), add() books their fold,
     run() folds ALL of them with msclip_colsum_multi (one launch per 96) into one fresh result buffer and hands every caller its
@@ -1761,15 +1596,6 @@ def bn_fold_bwd(G, w_raw, dshift, gamma, mean, var, eps):
     return dW, dgb[0], dgb[1]
 
 
-class PackItem(ctypes.Structure):
-    """msclip_pack_item (include/msclip_hip.h)."""
-    _fields_ = [("w", ctypes.c_void_p), ("g", ctypes.c_void_p), ("b", ctypes.c_void_p), ("mu", ctypes.c_void_p), ("var", ctypes.c_void_p),
-                ("w2", ctypes.c_void_p), ("g2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("mu2", ctypes.c_void_p), ("var2", ctypes.c_void_p),
-                ("out", ctypes.c_void_p), ("bias_out", ctypes.c_void_p), ("eps", ctypes.c_float), ("eps2", ctypes.c_float),
-                ("co", ctypes.c_int), ("ci", ctypes.c_int), ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("kpad", ctypes.c_int),
-                ("mode", ctypes.c_int), ("col0", ctypes.c_int), ("ld", ctypes.c_int), ("bias_mode", ctypes.c_int), ("bias_col0", ctypes.c_int)]
-
-
 class PackPlan:
     """Device-resident item table of msclip_pack_weights: every derived conv-side tensor described once (sources = the module's
     parameter storage, destinations = the engine's persistent operand tensors), re-run after every optimizer step."""
@@ -1840,12 +1666,6 @@ class PackPlan:
         _check(lib().msclip_pack_weights(_p(self.table), _p(self.blk_start), self.n_items, self.n_blocks, _stream()), "msclip_pack_weights")
 
 
-class TransposeItem(ctypes.Structure):
-    """msclip_transpose_item (include/msclip_hip.h)."""
-    _fields_ = [("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("ldi", ctypes.c_int), ("ldo", ctypes.c_int), ("M", ctypes.c_int),
-                ("C", ctypes.c_int)]
-
-
 class TransposePlan:
     """W^T of many bf16 matrices in ONE launch (msclip_transpose_bf16_multi): the sources' storage must persist (the engine's
     packed block weights, rewritten in place by the optimizer kernel); the outputs [C, M] are owned by the plan and rewritten
@@ -1877,13 +1697,6 @@ class TransposePlan:
         _check(lib().msclip_transpose_bf16_multi(_p(self.table), _p(self.blk_start), self.n_items, self.n_blocks, _stream()),
                "msclip_transpose_bf16_multi")
         return self.outs
-
-
-class AdamwTensor(ctypes.Structure):
-    """msclip_adamw_tensor (include/msclip_hip.h)."""
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("n", ctypes.c_longlong), ("lr", ctypes.c_float), ("weight_decay", ctypes.c_float),
-                ("pk", ctypes.c_void_p), ("pk_scale", ctypes.c_float), ("pk_f32", ctypes.c_int)]
 
 
 class AdamwPlan:

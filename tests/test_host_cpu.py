@@ -1,8 +1,11 @@
 """Host-side logic that needs no GPU: config surface, checkpoint ABI, weight packing folds (checked against the
 oracle), the implicit-GEMM chunk table semantics, the C-ABI library's exports, and the loud failure without a GPU."""
 import ctypes
+import keyword
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -10,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import ROOT, load_schema, synth_sd
-from msclip_amd import hip, packing as P, synth
+from msclip_amd import abi, hip, packing as P, synth
 from msclip_amd.clip_openai_pe_res_v1 import build_model, get_clip_model
 from msclip_amd.config import named_config
 from oracle import msclip_oracle as O
@@ -67,11 +70,14 @@ def test_no_cpu_fallback():
         model.encode_text(torch.zeros(1, 77, dtype=torch.long))
 
 
-def test_library_exports_every_declared_symbol():
+def _header_text():
     with open(os.path.join(ROOT, "include", "msclip_hip.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    declared = set(re.findall(r"\b(msclip_[a-z0-9_]+)\s*\(", text))
-    assert declared == set(hip.EXPORTS)
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+def test_library_exports_every_declared_symbol():
+    declared = set(re.findall(r"\b(msclip_[a-z0-9_]+)\s*\(", _header_text()))
+    assert declared == set(hip.EXPORTS) and len(hip.EXPORTS) == 103        # EXPORTS is derived from the header (msclip_amd/abi.py)
     if not os.path.exists(hip.LIB_PATH):
         hip.build()
     lib = ctypes.CDLL(hip.LIB_PATH)
@@ -84,40 +90,134 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(hip.GemmDesc) % 8 == 0 and hip.GemmDesc.ktab.offset % 8 == 0
 
 
+_MIRRORS = {"msclip_gemm_desc": "GemmDesc", "msclip_qkvattn_desc": "QkvAttnDesc", "msclip_bn_bwd_side": "BnBwdSide",
+            "msclip_fold_item": "FoldItem", "msclip_pack_item": "PackItem", "msclip_transpose_item": "TransposeItem",
+            "msclip_adamw_tensor": "AdamwTensor"}
+
+
+def test_struct_mirrors_match_the_c_compilers_layout(tmp_path):
+    """sizeof of every struct of the header and offsetof of every member, as a host C compiler sees the header (plain C99, no
+    device pass), against the ctypes mirrors that msclip_amd/abi.py generates: a packing, ordering or type mistake cannot pass."""
+    bodies = dict(re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}", _header_text()))
+    assert set(bodies) == set(_MIRRORS) == set(abi.load().structs)
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "msclip_hip.h"', "int main(void) {"]
+    expect = []
+    for cname, pyname in _MIRRORS.items():
+        mirror = getattr(hip, pyname)
+        assert mirror is hip._ABI.structs[cname]
+        assert len(mirror._fields_) == bodies[cname].count(";") + bodies[cname].count(",")     # one mirror field per C declarator
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        expect.append(f"{cname} {ctypes.sizeof(mirror)}")
+        for field, _ in mirror._fields_:
+            member = field[:-1] if keyword.iskeyword(field[:-1]) else field                        # `in_` mirrors the C member `in`
+            lines.append(f'  printf("{cname}.{member} %zu\\n", offsetof({cname}, {member}));')
+            expect.append(f"{cname}.{member} {getattr(mirror, field).offset}")
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    cc = shutil.which("cc") or "/opt/rocm/lib/llvm/bin/clang"
+    assert os.path.exists(cc), "no host C compiler (cc, or the clang that hipcc drives)"
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"),
+                    "-o", str(tmp_path / "layout")], check=True)
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
+    assert got == expect
+    assert "msclip_gemm_desc 280" in got and "msclip_gemm_desc.ktab 112" in got and "msclip_pack_item 144" in got
+    assert "msclip_adamw_tensor 64" in got and "msclip_transpose_item.in 0" in got
+
+
+def test_derived_signatures_are_the_headers():
+    """The mapping rule of msclip_amd/abi.py, pinned on literal signatures: a regression of the rule shows up here as a diff, not
+    on the GPU as a kernel that was handed a garbage pointer or row count."""
+    vp, ci, cf, ll, pp = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.POINTER(ctypes.c_void_p)
+    protos = abi.load().protos
+    pinned = {
+        "msclip_conv1x1_conv3x3s2": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp],
+        "msclip_convresblock48_s2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp],
+        "msclip_stem_dual_conv3x3s2": [vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp],
+        "msclip_layernorm_split": [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, cf, vp],
+        "msclip_adapter_combine_ln": [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp],
+        "msclip_dwpool": [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp],
+        "msclip_gather_rows": [vp, ll, vp, ci, ci, vp, ll, ci, ci, vp],
+        "msclip_gemm": [vp, vp],
+        "msclip_layernorm_bwd": [vp, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, ci, ci, ci, cf, vp, ci, vp, ci, vp],
+        "msclip_bn_bwd_fused": [ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ll, vp],
+        "msclip_plan_run": [vp, pp, ci, pp, ci],
+        "msclip_stream_create": [ci, pp],
+        "msclip_prepare_device": [],
+    }
+    for name, args in pinned.items():
+        assert protos[name] == (ci, args), name
+    assert protos["msclip_build_arch"] == (ctypes.c_char_p, []) and protos["msclip_plan_op_name"] == (ctypes.c_char_p, [vp, ci])
+    assert [n for n, (res, _) in protos.items() if res is not ci] == ["msclip_gemm_variant", "msclip_plan_op_name", "msclip_build_arch"]
+    # every type word of the header is accounted for: counted here from the text, independently of the reader
+    text = re.findall(r"\bmsclip_[a-z0-9_]+\s*\(([^)]*)\)", _header_text())
+    assert len(text) == len(protos) == 103
+    assert sum("long long" in t for t in text) == 18 and sum("float" in t for t in text) == 52
+    for word, ctype, count in (("long long", ll, 13), ("float", cf, 17)):                     # ... of them, passed by value
+        assert sum(bool(re.search(rf"\b{word}\s+\w", t)) for t in text) == sum(ctype in a for _, a in protos.values()) == count
+    assert sum(bool(re.search(r"\*\s*(const\s*)?\*", t)) for t in text) == sum(pp in a for _, a in protos.values()) == 6
+    if not os.path.exists(hip.LIB_PATH):
+        hip.build()
+    L = hip.lib()                                                    # ... and lib() binds exactly these
+    assert all(list(getattr(L, n).argtypes) == a and getattr(L, n).restype is r for n, (r, a) in protos.items())
+
+
+def test_library_without_a_declared_symbol_is_refused(monkeypatch):
+    if not os.path.exists(hip.LIB_PATH):
+        hip.build()
+    monkeypatch.setattr(hip, "_lib", None)
+    monkeypatch.setattr(hip, "_ABI", hip._ABI._replace(protos={**hip._ABI.protos, "msclip_not_built": (ctypes.c_int, [])}))
+    with pytest.raises(hip.HipUnavailable, match="msclip_not_built.*rebuild"):
+        hip.lib()
+
+
+_SNIPPET = "#define MSCLIP_ABI_VERSION 1\ntypedef struct msclip_t {\n  const float *a, *b;\n  int n;\n} msclip_t;\n%s\n"
+
+
+@pytest.mark.parametrize("bad", [
+    pytest.param("int msclip_f(unsigned n, void* stream);", id="unknown type word"),
+    pytest.param("typedef struct msclip_u { int n; float w[4]; } msclip_u;", id="array member"),
+    pytest.param("typedef struct msclip_u { int n : 3; } msclip_u;", id="bit-field"),
+    pytest.param("int msclip_f(int n, void* stream", id="unterminated prototype"),
+    pytest.param("int msclip_f(int n, void* stream\nint msclip_g(int n);", id="unterminated prototype, another one behind it"),
+    pytest.param("int msclip_f(const msclip_v* d);", id="struct that was never declared"),
+    pytest.param("int msclip_f(msclip_t d);", id="struct by value"),
+    pytest.param("long long msclip_f(int n);", id="return type outside int / const char*"),
+    pytest.param("int msclip_f(int n);\nint msclip_f(int n);", id="declared twice"),
+])
+def test_header_reader_refuses_what_it_does_not_understand(bad):
+    ok = abi.parse(_SNIPPET % "int msclip_f(const msclip_t* d, long long n, float w, void* const* streams);")
+    vp = ctypes.c_void_p
+    assert ok.version == 1 and ok.protos == {"msclip_f": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_float, ctypes.POINTER(vp)])}
+    assert ok.structs["msclip_t"]._fields_ == [("a", vp), ("b", vp), ("n", ctypes.c_int)]
+    with pytest.raises(abi.AbiError):
+        abi.parse(_SNIPPET % bad)
+    with pytest.raises(abi.AbiError):
+        abi.parse((_SNIPPET % "").replace("#define MSCLIP_ABI_VERSION 1", ""))
+
+
 def test_entry_points_reject_bad_arguments_before_launching():
     """Argument validation of the C ABI runs on the host, before any launch: null pointers, unsupported channel
     counts, sizes whose byte offsets would not fit the kernels' 32-bit buffer addressing (include/msclip_hip.h)."""
     if not os.path.exists(hip.LIB_PATH):
         hip.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib = hip.lib()                                                  # (loading and binding need no GPU)
     EINVAL = -1
     buf = ctypes.create_string_buffer(64)
-    p = ctypes.cast(buf, vp)
-    lib.msclip_conv1x1_conv3x3s2.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    p = ctypes.cast(buf, ctypes.c_void_p)
     assert lib.msclip_conv1x1_conv3x3s2(None, p, p, p, p, p, 1, 8, 8, 48, None) == EINVAL          # null input
     assert lib.msclip_conv1x1_conv3x3s2(p, p, p, p, p, p, 1, 8, 8, 64, None) == EINVAL             # Cout not 48 / 96
     assert lib.msclip_conv1x1_conv3x3s2(p, p, p, p, p, p, 4096, 112, 112, 48, None) == EINVAL      # input >= 2 GiB
-    lib.msclip_convresblock48_s2.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     assert lib.msclip_convresblock48_s2(p, p, p, p, p, p, None, p, p, 1, 8, 8, None) == EINVAL     # null shortcut weights
     assert lib.msclip_convresblock48_s2(p, p, p, p, p, p, p, p, p, 0, 8, 8, None) == EINVAL        # empty batch
-    lib.msclip_stem_dual_conv3x3s2.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     assert lib.msclip_stem_dual_conv3x3s2(p, 0, p, p, p, p, p, p, 1, 224, 224, 32, None) == EINVAL
     assert lib.msclip_stem_dual_conv3x3s2(p, 0, p, p, p, p, p, p, 4000, 224, 224, 96, None) == EINVAL   # image >= 2 GiB
-    lib.msclip_layernorm_split.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ctypes.c_float, vp]
     assert lib.msclip_layernorm_split(p, 768, p, p, p, p, 9, p, 768, 0, 8, 768, 1e-12, None) == EINVAL   # split > M
     assert lib.msclip_layernorm_split(p, 770, p, p, p, p, 4, p, 768, 0, 8, 768, 1e-12, None) == EINVAL   # ldx % 4
-    lib.msclip_adapter_combine_ln.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
     assert lib.msclip_adapter_combine_ln(p, 768, p, 768, p, p, p, p, p, 768, 1, 51, 7, 768, 1, 1e-12, None) == EINVAL   # L != g*g+1
     assert lib.msclip_adapter_combine_ln(p, 768, p, 768, p, p, p, p, p, 768, 1, 50, 7, 768, 1, 1e-12, None) == EINVAL   # in place
-    lib.msclip_dwpool.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
     assert lib.msclip_dwpool(p, p, p, 48, 1, 112, 112, 48, 5, None) == EINVAL                      # H % k
-    lib.msclip_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     assert lib.msclip_gather_rows(None, 3072, None, 1, 0, p, 3072, 4, 3072, None) == EINVAL        # null input
     assert lib.msclip_gather_rows(p, 3072, None, 1, 0, p, 3072, 4, 3000, None) == EINVAL           # rows not 16-byte pieces
     assert lib.msclip_gather_rows(p, 3072, None, 1, 0, p, 3072, 0, 3072, None) == EINVAL           # no rows
-    lib.msclip_gemm.argtypes = [vp, vp]
     assert lib.msclip_gemm(None, None) == EINVAL
 
 
