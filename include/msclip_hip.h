@@ -452,6 +452,8 @@ int msclip_attention_lastq(const void* q, int ldqc, const void* qkv, int ldq, vo
  * gradient dout (all bf16, same layouts as the forward).  L <= 96: the whole head resident in LDS; 97-208 (the 197-token
  * grid of ViT-B/16): query axis in blocks of 32, dK / dV accumulated in registers across the blocks; 209-272 (the 257-token
  * grid of ViT-L/14): the same with K^T read transposed out of the row-major K instead of a resident copy.
+ * o must be a valid pointer but is not read: softmax's delta is summed from P and dP in fp32, not from dout and the rounded o
+ * (csrc/attention_bwd.hip).
  * colsum_part (NULL: off; L <= 96 only): fp32 [nsamples][3 * heads * 64], row b = the sums over sample b's tokens of its dqkv
  * rows (fp32 values, fixed order) -- folded over the samples (msclip_colsum) they are the in_proj bias gradient, without a second
  * pass over dqkv. */

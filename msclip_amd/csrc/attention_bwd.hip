@@ -5,12 +5,17 @@
 // down (attn_bwd_qb_kernel), and 209-272 tokens (the 257-token grid of ViT-L/14) its variant without a resident K^T.
 //
 //   S  = Q K^T (q pre-scaled by the packed in_proj weight),  P = softmax(S),  O = P V            (recomputed / given)
-//   dV = P^T dO      dP = dO V^T      dS = P o (dP - delta),  delta_q = sum_d dO[q][d] O[q][d]
+//   dV = P^T dO      dP = dO V^T      dS = P o (dP - delta),  delta_q = sum_k P[q][k] dP[q][k]
 //   dQ = dS K        dK = dS^T Q
+// delta is summed from the fp32 P and dP of the row, NOT taken as sum_d dO[q][d] O[q][d] from the stored output: O is bf16, and
+// with a rounded O the rows of dS stop summing to zero -- every dS[q][k] is off by P[q][k] * (error of delta_q), the same sign
+// along the row.  The token sums of dK (the k third of in_proj's bias gradient, zero in exact arithmetic) then carry a residue
+// several times the rounding noise of everything else, and dK's rows a common offset (tests/test_gpu_train_full.py found it;
+// test_gpu_train.py::test_attention_backward_rows_of_dS_sum_to_zero).  `o` is therefore no longer read.
 //
 // The MFMA computes D[i][j] = sum_k A[i][k] B[j][k] from two K-contiguous row operands, lane (j = lane % 16,
 // quad = lane / 16) holding D[4*quad + r][j].  So S, dP are formed TRANSPOSED (A = K / V rows, B = Q / dO rows): a lane
-// owns one query and 4 keys per tile, the softmax statistics of a query are an in-lane reduction plus two quad
+// owns one query and 4 keys per tile, the softmax statistics and delta of a query are an in-lane reduction plus two quad
 // exchanges, and dS^T = P^T o (dP^T - delta) is element-wise in registers.  The three gradients contract over tokens,
 // so their operands are the TRANSPOSED tensors: Q^T, K^T, dO^T are built while loading, P^T / dS / dS^T are written to
 // LDS from the accumulator layout; the outputs come out as dV^T, dK^T, dQ^T tiles, i.e. 4 consecutive head-dim elements
@@ -57,11 +62,10 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
   //  its token-contracting operands from the row-major images with ds_read_b64_tr_b16.)
   bf16_t* P = dO + LP * RS;                            // [query][key]   (LP x LS)  (P^T / dS^T are read through ds_read_b64_tr_b16 too)
   bf16_t* dS = P + LP * LS;                            // [query][key]
-  float* delta = (float*)(dS + LP * LS);               // [LP]
   // csum_part: the token sums of every phase-2 output tile (16 head-dim columns each), two buffers (pair parity): the in_proj
   // bias gradient's share of this (sample, head) leaves with the pair instead of a second pass over dqkv [M, 3 D]
   constexpr int TSUM = 3 * 4 * NT16 * 16;
-  float* tsum = delta + LP;                            // [2][which][head-dim tile][token tile][16]
+  float* tsum = (float*)(dS + LP * LS);                // [2][which][head-dim tile][token tile][16]
   int tbuf = 0;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -78,11 +82,11 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
   }
   // Round 5: PERSISTENT workgroups with a register prefetch.  The head's images fill 92-155 KB of LDS, so a CU holds one
   // workgroup, and with one (sample, head) pair per workgroup the ~3 us of its global loads were exposed in front of ~2.5 us of
-  // work, 24-48 times per CU and launch.  Now a workgroup walks pairs blockIdx.x, + pblocks, ...: the five 16-byte pieces per
-  // thread of pair i + 1 (q, k, v, dO, O) are requested right after pair i's images are in LDS and land under its two phases.
+  // work, 24-48 times per CU and launch.  Now a workgroup walks pairs blockIdx.x, + pblocks, ...: the four 16-byte pieces per
+  // thread of pair i + 1 (q, k, v, dO) are requested right after pair i's images are in LDS and land under its two phases.
   constexpr int NI = (LP * 8 + 64 * BW - 1) / (64 * BW);      // load iterations per thread (1: 64 tokens, 2: 96)
   const int npairs = nsamples * H;
-  uint4 pq[NI], pk[NI], pv[NI], pd[NI], po[NI];
+  uint4 pq[NI], pk[NI], pv[NI], pd[NI];
   auto pair_rows = [&](int pair, int& c0, int& L, int& h) {
     const int b = pair / H;
     h = pair - b * H;
@@ -91,18 +95,16 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
   };
   auto fetch = [&](int c0, int L, int h) {
     const bf16_t* qb = qkv + (size_t)c0 * ldq + h * 64;
-    const bf16_t* ob = o + (size_t)c0 * ldo + h * 64;
     const bf16_t* db = dout + (size_t)c0 * ldo + h * 64;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + i * 64 * BW, r = idx >> 3, c = idx & 7;
-      pq[i] = pk[i] = pv[i] = pd[i] = po[i] = make_uint4(0, 0, 0, 0);
+      pq[i] = pk[i] = pv[i] = pd[i] = make_uint4(0, 0, 0, 0);
       if (idx < LP * 8 && r < L) {
         pq[i] = *(const uint4*)(qb + (size_t)r * ldq + c * 8);
         pk[i] = *(const uint4*)(qb + (size_t)r * ldq + H * 64 + c * 8);
         pv[i] = *(const uint4*)(qb + (size_t)r * ldq + 2 * H * 64 + c * 8);
         pd[i] = *(const uint4*)(db + (size_t)r * ldo + c * 8);
-        po[i] = *(const uint4*)(ob + (size_t)r * ldo + c * 8);
       }
     }
   };
@@ -115,27 +117,16 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
   for (; pair < npairs; pair += pblocks) {
   const size_t row0 = (size_t)c0;
   const int hcur = h, bcur = pair / H;
-  // ---- the prefetched pieces -> LDS: thread -> (token r, 16-byte chunk c); row-major and transposed images, delta
+  // ---- the prefetched pieces -> LDS: thread -> (token r, 16-byte chunk c)
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int idx = tid + i * 64 * BW;
     if (idx >= LP * 8) continue;
     const int r = idx >> 3, c = idx & 7;
-    const uint4 q4 = pq[i], k4 = pk[i], v4 = pv[i], d4 = pd[i], o4 = po[i];
-    *(uint4*)(Q + r * RS + c * 8) = q4;
-    *(uint4*)(K + r * RS + c * 8) = k4;
-    *(uint4*)(V + r * RS + c * 8) = v4;
-    *(uint4*)(dO + r * RS + c * 8) = d4;
-    float fd[8], fo[8];
-    unpack_bf16x8(d4, fd);
-    unpack_bf16x8(o4, fo);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += fd[e] * fo[e];
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (c == 0) delta[r] = s;
+    *(uint4*)(Q + r * RS + c * 8) = pq[i];
+    *(uint4*)(K + r * RS + c * 8) = pk[i];
+    *(uint4*)(V + r * RS + c * 8) = pv[i];
+    *(uint4*)(dO + r * RS + c * 8) = pd[i];
   }
   const int Lcur = L;
   {                                                    // the next pair's pieces: in flight under this pair's two phases
@@ -198,7 +189,6 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = sum > 0.f ? 1.f / sum : 0.f;
-    const float dl = delta[query];
     f32x4 dpt[NT16];
     {   // dP^T tiles the same way
       bf16x8 vf[NT16][2];
@@ -216,6 +206,14 @@ __global__ __launch_bounds__(64 * BW) void attn_bwd_kernel(const bf16_t* __restr
       }
       __builtin_amdgcn_sched_barrier(0);
     }
+    float dl = 0.f;                                     // delta of this lane's query: sum over its keys of P o dP (masked keys: P = 0)
+#pragma unroll
+    for (int kt = 0; kt < NT16; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dl += st[kt][r] * dpt[kt][r];
+    dl += __shfl_xor(dl, 16, 64);
+    dl += __shfl_xor(dl, 32, 64);
+    dl *= inv;
 #pragma unroll
     for (int kt = 0; kt < NT16; ++kt) {
       const f32x4 dp = dpt[kt];
@@ -309,7 +307,7 @@ int launch_bwd(const void* qkv, const void* o, const void* dout, void* dqkv, int
   // 8-wave workgroup its four query tiles left half the waves idle in phase 1, and nothing ran under its barriers and loads);
   // 96 tokens: 94 KB -> one workgroup of 8 waves
   constexpr int BW = NT16 <= 4 ? 4 : 8;
-  const size_t lds = (size_t)(4 * LP * RS + 2 * LP * LS) * 2 + LP * 4 + 2 * (3 * 4 * NT16 * 16) * 4;
+  const size_t lds = (size_t)(4 * LP * RS + 2 * LP * LS) * 2 + 2 * (3 * 4 * NT16 * 16) * 4;
   bool attr_ok = true;
   if (lds > 65536) MSCLIP_LDS_ATTR((&attn_bwd_kernel<NT16, CAUSAL, BW>), lds, attr_ok);
   (void)attr_ok;
@@ -327,11 +325,11 @@ int launch_bwd(const void* qkv, const void* o, const void* dout, void* dqkv, int
 // Longer sequences (96 < L <= 208: the 197-token grid of ViT-B/16).  P^T, dS and dS^T of a whole head no longer fit the
 // LDS next to the operands (3 x 208 x 216 bf16 = 270 KB), so the QUERY axis is processed in blocks of 32:
 //   resident for the head:  K, V row-major, K^T                                     (87 KB at L = 197)
-//   per query block:        Q, dO rows and their transposes, delta, P^T / dS^T [key][32], dS [32][key]   (66 KB)
+//   per query block:        Q, dO rows and their transposes, P^T / dS^T [key][32], dS [32][key]   (66 KB)
 // dQ of a block is complete after the block (it contracts over keys); dV^T and dK^T contract over queries and are
 // accumulated in registers across the blocks (2 * 4 * NT16 tiles of 16 x 16 over the QB_WAVES waves: NT16 accumulators
 // per wave at eight) and stored once at the end.  Phase 1 of a block has only two 16-query tiles, so a wave takes (query
-// tile, one of QB_WAVES / 2 parts of the key tiles) and the parts exchange the row maximum and the row sum through LDS.
+// tile, one of QB_WAVES / 2 parts of the key tiles) and the parts exchange the row maximum, the row sum and their shares of delta through LDS.
 // The key axis is padded to a multiple of 32 (one MFMA k-step) with zero columns in K^T and dS.
 // ------------------------------------------------------------------------------------------------------------
 // Waves per workgroup of the query-blocked kernel: its 153 KB of LDS also mean one workgroup per CU.
@@ -342,7 +340,7 @@ constexpr int QB_WAVES = 8;
 // K^T fragments from the row-major K with ds_read_b64_tr_b16 (ld_tr8, as attn_bwd_kernel's phase 2 does), and K gets the
 // k-step padding rows [LP, LPK) (zero) instead:
 //   K [288][72] 41.5 KB + V [272][72] 39.2 KB + Q/dO blocks 9.2 KB + their transposes 10.2 KB + P^T/dS^T [272][40] 43.5 KB
-//   + dS [32][296] 18.9 KB + delta / statistics 1.2 KB = 163 712 B of the 163 840.
+//   + dS [32][296] 18.9 KB + statistics 1 KB = 163 584 B of the 163 840.
 template <int NT16, bool CAUSAL, bool KTR = false>
 __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                           const bf16_t* __restrict__ dout, bf16_t* __restrict__ dqkv, int L,
@@ -363,15 +361,13 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
   bf16_t* PT = dOT + 64 * QS;                          // [LP][QS]   (key, query in block)
   bf16_t* dST = PT + LP * QS;
   bf16_t* dS = dST + LP * QS;                          // [QB][LS]
-  float* delta = (float*)(dS + QB * LS);               // [QB]
-  float* red = delta + QB;                             // [2 stats][KH key parts][QB]
+  float* red = (float*)(dS + QB * LS);                 // [2 stats][KH key parts][QB]  (the maxima's slots carry the delta shares afterwards)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
   const size_t row0 = (size_t)b * L;
   const bf16_t* qb = qkv + row0 * ldq + h * 64;
-  const bf16_t* ob = o + row0 * ldo + h * 64;
   const bf16_t* db = dout + row0 * ldo + h * 64;
   bf16_t* gb = dqkv + row0 * ldq + h * 64;
 
@@ -441,11 +437,10 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
     __syncthreads();                                   // previous block's phase 2 is done with the block buffers
     if (tid < QB * 8) {
       const int r = tid >> 3, c = tid & 7, q = q0 + r;
-      uint4 q4 = make_uint4(0, 0, 0, 0), d4 = q4, o4 = q4;
+      uint4 q4 = make_uint4(0, 0, 0, 0), d4 = q4;
       if (q < L) {
         q4 = *(const uint4*)(qb + (size_t)q * ldq + c * 8);
         d4 = *(const uint4*)(db + (size_t)q * ldo + c * 8);
-        o4 = *(const uint4*)(ob + (size_t)q * ldo + c * 8);
       }
       *(uint4*)(Qb + r * RS + c * 8) = q4;
       *(uint4*)(dOb + r * RS + c * 8) = d4;
@@ -457,16 +452,6 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
         dOT[(c * 8 + 2 * e) * QS + r] = (bf16_t)(dw[e] & 0xffff);
         dOT[(c * 8 + 2 * e + 1) * QS + r] = (bf16_t)(dw[e] >> 16);
       }
-      float fd[8], fo[8];
-      unpack_bf16x8(d4, fd);
-      unpack_bf16x8(o4, fo);
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += fd[e] * fo[e];
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      if (c == 0) delta[r] = s;
     }
     __syncthreads();
 
@@ -515,12 +500,31 @@ __global__ __launch_bounds__(64 * QB_WAVES) void attn_bwd_qb_kernel(const bf16_t
 #pragma unroll
       for (int p = 1; p < KH; ++p) sum += red[(KH + p) * QB + qi];
       const float inv = sum > 0.f ? 1.f / sum : 0.f;
-      const float dl = delta[qi];
+      // dP^T of this part's key tiles, and delta = sum over ALL keys of P o dP: this part's share, then the parts' through LDS
+      f32x4 dpt[NK0];
+      float dl = 0.f;
 #pragma unroll
       for (int i = 0; i < NK0; ++i) {
         const int kt = kt0 + i;
         if (kt < kt1) {
-          const f32x4 dp = mma(f32x4{0.f, 0.f, 0.f, 0.f}, V + kt * 16 * RS, RS, dOb + qt * 16 * RS, RS, K2{});
+          dpt[i] = mma(f32x4{0.f, 0.f, 0.f, 0.f}, V + kt * 16 * RS, RS, dOb + qt * 16 * RS, RS, K2{});
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dl += st[i][r] * dpt[i][r];
+        }
+      }
+      dl += __shfl_xor(dl, 16, 64);
+      dl += __shfl_xor(dl, 32, 64);
+      if (quad == 0) red[kh * QB + qi] = dl;           // (every wave read the maxima before the barrier above)
+      __syncthreads();
+      dl = red[qi];
+#pragma unroll
+      for (int p = 1; p < KH; ++p) dl += red[p * QB + qi];
+      dl *= inv;
+#pragma unroll
+      for (int i = 0; i < NK0; ++i) {
+        const int kt = kt0 + i;
+        if (kt < kt1) {
+          const f32x4 dp = dpt[i];
           float ds[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -606,8 +610,8 @@ template <int NT16, bool CAUSAL, bool KTR = false>
 int launch_bwd_qb(const void* qkv, const void* o, const void* dout, void* dqkv, int nsamples, int L, int H, int ldq, int ldo,
                   hipStream_t st) {
   constexpr int LP = NT16 * 16, LPK = (LP + 31) / 32 * 32, LS = LPK + 8, QB = 32, QS = QB + 8;
-  constexpr size_t lds = KTR ? (size_t)(LPK * RS + LP * RS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + (1 + QB_WAVES) * QB * 4
-                             : (size_t)(2 * LP * RS + 64 * LS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + (1 + QB_WAVES) * QB * 4;
+  constexpr size_t lds = KTR ? (size_t)(LPK * RS + LP * RS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + QB_WAVES * QB * 4
+                             : (size_t)(2 * LP * RS + 64 * LS + 2 * QB * RS + 2 * 64 * QS + 2 * LP * QS + QB * LS) * 2 + QB_WAVES * QB * 4;
   static_assert(lds <= 160 * 1024, "the query-blocked form must fit one CU's LDS");
   bool attr_ok = true;
   MSCLIP_LDS_ATTR((&attn_bwd_qb_kernel<NT16, CAUSAL, KTR>), lds, attr_ok);

@@ -16,6 +16,10 @@ synthetic weights into it, and stores its outputs under tests/golden/;
 tests/test_oracle_golden.py checks this oracle against those vectors
 (fp32, <=2e-5 abs on unit-norm features) and tests/test_oracle_vs_reference.py
 re-checks against the live import when the reference tree is present.
+The BACKWARD is pinned too: oracle/autograd.py differentiates contrastive_loss(forward(...)) of this file, and
+tests/test_oracle_autograd_cpu.py checks every gradient tensor against the fixtures captured from autograd of the real
+reference (tests/golden/*.grads*.npz), in eval mode (the default here, from the running statistics) and with train-mode
+BatchNorm (Arch.bn_train: batch statistics, as the reference's modules run in train()).
 The symmetric cross-entropy (contrastive_loss) has NO reference implementation
 (SURVEY.md s8 a14): parity unpinned, pinned only against
 torch.nn.functional.cross_entropy.
@@ -51,6 +55,7 @@ class Arch:
     t2b_usecls: bool = True                              # PRALLEL_T2B_USECLS
     share_from_layer: int = 1                            # N_LAYERS
     patch_conv: bool = False                             # EARLY_CONV off: plain patch convolution `visual.conv1` (M.py:2502-2508)
+    bn_train: bool = False                               # BatchNorm in train() mode: batch statistics (oracle/autograd.py); eval is the default
 
     @property
     def grid(self):
@@ -103,9 +108,13 @@ def quick_gelu(x: Tensor) -> Tensor:
     return x * torch.sigmoid(1.702 * x)
 
 
-def batch_norm(x: Tensor, sd: SD, prefix: str, eps: float) -> Tensor:
-    """Eval-mode BatchNorm2d from running stats on an NCHW tensor."""
+def batch_norm(x: Tensor, sd: SD, prefix: str, eps: float, train: bool = False) -> Tensor:
+    """BatchNorm2d on an NCHW tensor.  Eval mode (the default): from the running statistics.  train=True: nn.BatchNorm2d in
+    train() mode -- normalised with the statistics of this batch over (N, H, W), biased variance; the running statistics are
+    neither read nor updated here."""
     w, b = sd[prefix + ".weight"], sd[prefix + ".bias"]
+    if train:
+        return F.batch_norm(x, None, None, w, b, True, 0.0, eps)
     mu, var = sd[prefix + ".running_mean"], sd[prefix + ".running_var"]
     scale = w / torch.sqrt(var + eps)
     return x * scale[None, :, None, None] + (b - mu * scale)[None, :, None, None]
@@ -161,13 +170,13 @@ def stem(img: Tensor, sd: SD, arch: Arch, taps: dict = None) -> Tensor:
     1x1 last_conv without BN/ReLU.  NCHW in, [B, width, g, g] out."""
     p = "visual.transformer.resblocks.0"
     x = F.conv2d(img, sd[p + ".conv1.weight"], stride=2, padding=1)
-    x = F.relu(batch_norm(x, sd, p + ".bn1", 1e-5))
+    x = F.relu(batch_norm(x, sd, p + ".bn1", 1e-5, arch.bn_train))
     if taps is not None:
         taps["stem_conv1"] = x
     for i, s in enumerate(arch.stem_strides):
         q = f"{p}.resnet_stage.conv_{i}"
-        main = batch_norm(F.conv2d(x, sd[q + ".conv1.weight"], stride=s, padding=1), sd, q + ".bn1", 1e-5)
-        short = batch_norm(F.conv2d(x, sd[q + ".downsample.0.weight"], stride=s), sd, q + ".downsample.1", 1e-5)
+        main = batch_norm(F.conv2d(x, sd[q + ".conv1.weight"], stride=s, padding=1), sd, q + ".bn1", 1e-5, arch.bn_train)
+        short = batch_norm(F.conv2d(x, sd[q + ".downsample.0.weight"], stride=s), sd, q + ".downsample.1", 1e-5, arch.bn_train)
         x = F.relu(main + short)
         if taps is not None:
             taps[f"stem_stage{i}"] = x
@@ -184,12 +193,12 @@ def parallel_stage(x: Tensor, sd: SD, arch: Arch, j: int) -> Tensor:
     s = arch.parallel_strides[j]
     if j == 0:
         x = F.conv2d(x, sd[p + ".conv.weight"], stride=s, padding=1)
-        return F.relu(batch_norm(x, sd, p + ".bn", 1e-5))
+        return F.relu(batch_norm(x, sd, p + ".bn", 1e-5, arch.bn_train))
     q = p + ".resnet_stage.conv_0"
-    y = F.relu(batch_norm(F.conv2d(x, sd[q + ".conv1.weight"]), sd, q + ".bn1", 1e-6))
-    y = F.relu(batch_norm(F.conv2d(y, sd[q + ".conv2.weight"], stride=s, padding=1), sd, q + ".bn2", 1e-6))
-    y = batch_norm(F.conv2d(y, sd[q + ".conv3.weight"]), sd, q + ".bn3", 1e-6)
-    r = batch_norm(F.conv2d(x, sd[q + ".residual_conv.weight"], stride=s), sd, q + ".residual_bn", 1e-6)
+    y = F.relu(batch_norm(F.conv2d(x, sd[q + ".conv1.weight"]), sd, q + ".bn1", 1e-6, arch.bn_train))
+    y = F.relu(batch_norm(F.conv2d(y, sd[q + ".conv2.weight"], stride=s, padding=1), sd, q + ".bn2", 1e-6, arch.bn_train))
+    y = batch_norm(F.conv2d(y, sd[q + ".conv3.weight"]), sd, q + ".bn3", 1e-6, arch.bn_train)
+    r = batch_norm(F.conv2d(x, sd[q + ".residual_conv.weight"], stride=s), sd, q + ".residual_bn", 1e-6, arch.bn_train)
     return F.relu(y + r)
 
 
@@ -204,14 +213,14 @@ def lateral_adapter(top: Tensor, x: Tensor, sd: SD, arch: Arch, j: int) -> Tenso
     g = arch.grid
     k, s, pad = arch.t2b_kernels[j], arch.t2b_strides[j], arch.t2b_paddings[j]
     t = F.conv2d(top, sd[p + ".top2bottom_dw_conv.conv.weight"], stride=s, padding=pad, groups=top.shape[1])
-    t = batch_norm(t, sd, p + ".top2bottom_dw_conv.bn", 1e-5)
+    t = batch_norm(t, sd, p + ".top2bottom_dw_conv.bn", 1e-5, arch.bn_train)
     t = F.conv2d(t, sd[p + ".top2bottom_pw_conv.conv.weight"])
     assert t.shape[-2:] == (g, g), (t.shape, g, k)
     t = t.flatten(2).transpose(1, 2)                                   # b (h w) c
     cls, grid = x[:, :1], x[:, 1:]
     grid = grid.transpose(1, 2).reshape(B, C, g, g)
     bo = F.conv2d(grid, sd[p + ".bottom_dw_conv.conv.weight"], padding=1, groups=C)
-    bo = batch_norm(bo, sd, p + ".bottom_dw_conv.bn", 1e-5).flatten(2).transpose(1, 2)
+    bo = batch_norm(bo, sd, p + ".bottom_dw_conv.bn", 1e-5, arch.bn_train).flatten(2).transpose(1, 2)
     bo = torch.cat([cls, bo], 1)
     t = torch.cat([cls if arch.t2b_usecls else torch.zeros_like(cls), t], 1)
     return layer_norm(bo + t, sd[p + ".ln_adapt.weight"], sd[p + ".ln_adapt.bias"])
