@@ -22,6 +22,11 @@ EXPORTS = tuple(_ABI.protos)
 GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor = (_ABI.structs[n] for n in (
     "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item", "msclip_transpose_item",
     "msclip_adamw_tensor"))
+# include/msclip_hip_train.h: the training entry points declared after msclip_hip.h was frozen, in a table of their own
+_TRAIN_ABI = abi.load(abi.TRAIN_HEADER, abi.TRAIN_VERSION_MACRO)
+TRAIN_ABI_VERSION = _TRAIN_ABI.version
+TRAIN_EXPORTS = tuple(_TRAIN_ABI.protos)
+AccumTensor = _TRAIN_ABI.structs["msclip_accum_tensor"]
 
 
 class HipUnavailable(RuntimeError):
@@ -50,15 +55,19 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise HipUnavailable(f"{LIB_PATH} is missing: run msclip_amd/csrc/build.sh (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _ABI.protos.items():             # abi.py states the C type -> ctypes rule
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_hip.h declares: rebuild "
-                                     "(bash msclip_amd/csrc/build.sh)")
-            fn.restype, fn.argtypes = restype, argtypes
+        for header, table in (("msclip_hip.h", _ABI), ("msclip_hip_train.h", _TRAIN_ABI)):
+            for name, (restype, argtypes) in table.protos.items():         # abi.py states the C type -> ctypes rule
+                fn = getattr(L, name, None)
+                if fn is None:
+                    raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/{header} declares: rebuild "
+                                         "(bash msclip_amd/csrc/build.sh)")
+                fn.restype, fn.argtypes = restype, argtypes
         if L.msclip_abi_version() != ABI_VERSION:          # a stale build of the library (the struct layouts / entry points moved on)
             raise HipUnavailable(f"{LIB_PATH} has ABI version {L.msclip_abi_version()}, this binding needs {ABI_VERSION}: rebuild "
                                  "(bash msclip_amd/csrc/build.sh)")
+        if L.msclip_train_abi_version() != TRAIN_ABI_VERSION:
+            raise HipUnavailable(f"{LIB_PATH} has training ABI version {L.msclip_train_abi_version()}, this binding needs "
+                                 f"{TRAIN_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1751,3 +1760,38 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
     _check(lib().msclip_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step, _stream()),
            "msclip_adamw")
+
+
+class AccumulatePlan:
+    """The host-side tensor table of msclip_grad_accumulate (include/msclip_hip_train.h): built once over the persistent fp32
+    accumulators, per chunk only the gradient addresses are re-pointed.  accs: contiguous fp32 tensors (any 4-byte-aligned
+    views); empty ones take no part."""
+
+    def __init__(self, accs):
+        for t in accs:
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.is_contiguous())
+        self.accs = list(accs)
+        self.live = [i for i, t in enumerate(self.accs) if t.numel() > 0]
+        self.n = len(self.live)
+        self.arr = (AccumTensor * max(self.n, 1))()
+        self.device = self.accs[0].device if self.accs else None
+        for a, i in zip(self.arr, self.live):
+            a.acc, a.n = self.accs[i].data_ptr(), self.accs[i].numel()
+
+    def run(self, grads, mode):
+        """grads: one contiguous fp32 tensor per accumulator, same element counts.  mode 0: acc = g; mode 1: acc += g."""
+        assert len(grads) == len(self.accs) and mode in (0, 1)
+        for a, i in zip(self.arr, self.live):
+            g = grads[i]
+            assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() == a.n and g.device == self.device, \
+                (g.dtype, g.is_contiguous(), g.numel(), a.n)
+            a.g = g.data_ptr()
+        if not self.n:
+            return
+        with torch.cuda.device(self.device):
+            _check(lib().msclip_grad_accumulate(self.arr, self.n, mode, _stream()), "msclip_grad_accumulate")
+
+
+def grad_accumulate(accs, grads, mode):
+    """One msclip_grad_accumulate call over lists of fp32 tensors (see AccumulatePlan)."""
+    AccumulatePlan(accs).run(grads, mode)

@@ -78,7 +78,10 @@ class TrainStep:
         finally:
             self.eng.force_unfused = False
 
-    def _forward(self, img, tok):
+    def _forward(self, img, tok, head=True, update_stats=True):
+        """head=False (accumulate()): stop in front of the contrastive head and return the two gather payloads; the saved
+        activations then wait for a backward(_dfeat=...).  update_stats=False: train-mode BatchNorm normalises with the
+        batch statistics but leaves the module's running statistics alone (accumulate()'s feature pass)."""
         e = self.eng
         e.refresh()
         with torch.cuda.device(e.dev), torch.no_grad():
@@ -258,7 +261,7 @@ class TrainStep:
                 sv["layers"][i] = L
                 Xc = XN
             e.force_unfused = False
-            if cb is not None:
+            if cb is not None and update_stats:
                 cb.update_running_stats()
             # ---- heads + loss
             if sv.get("compact") is not None:
@@ -295,6 +298,9 @@ class TrainStep:
             s_dev = e.model.logit_scale.detach().float().exp()
             sv["scale"] = s_dev
             pi, pt = split(sv["fv"] * s_dev), split(sv["ft"])
+            if not head:
+                self.saved = sv
+                return pi, pt
             if C.comm.collectives:
                 allpi, hi_ = C.gather_rows_async(pi)
                 allpt, ht_ = C.gather_rows_async(pt)
@@ -333,7 +339,7 @@ class TrainStep:
 
     # ------------------------------------------------------------------ backward
     @hip.off_default_stream
-    def backward(self, reduce=True, bucket_bytes=64 << 20, clone=False):
+    def backward(self, reduce=True, bucket_bytes=64 << 20, clone=False, _dfeat=None):
         """-> {reference state_dict key: fp32 gradient} for every parameter of the slice (shared tensors under their
         visual.* key; the text-tower aliases are the same Parameter objects).  Under N > 1 ranks (and reduce=True) the
         gradients are averaged over the ranks as the reference's DDP wrapper would: every gradient goes into a
@@ -343,14 +349,16 @@ class TrainStep:
         backward() on this device overwrites (in-place 1 / world scaling and split-K writes included): call step() before the
         next backward, or pass clone=True to own the tensors (gradient accumulation over micro-batches, comparing two backward
         passes, two TrainSteps on one device).  step() refuses stale views (comm.GradViews.check_fresh).  At world size 1 the
-        gradients are fresh tensors either way."""
+        gradients are fresh tensors either way.
+        _dfeat (accumulate() only): (d loss / d image features, d loss / d text features, d loss / d logit_scale) of a
+        forward that stopped in front of the head; the head's own backward is skipped, everything below it is the same."""
         e, sv = self.eng, getattr(self, "saved", None)
         if sv is None:
             raise RuntimeError("TrainStep.backward() needs the activations of a TrainStep.forward() that has not been "
                                "differentiated yet (call forward first; one backward per forward)")
         dev, D, E = e.dev, e.D, e.E
         with torch.cuda.device(dev), torch.no_grad():
-            Bi, Bt, Mv, M, n, off = sv["Bi"], sv["Bt"], sv["Mv"], sv["M"], sv["n"], sv["off"]
+            Bi, Bt, Mv, M = sv["Bi"], sv["Bt"], sv["Mv"], sv["M"]
             reducer = C.GradReducer(bucket_bytes) if (reduce and C.comm.collectives) else None
             self.reducer = reducer
 
@@ -398,27 +406,16 @@ class TrainStep:
                 flush_wgrads()
                 pending.append((k, gradgemm.WgradJob(dy, x, rows, post=post), shape))
             # ---- contrastive head: dL/dS blocks of this rank's image rows and caption rows
-            npad = (n + 63) // 64 * 64
-            wgt = 1.0 / (2.0 * n)
-
-            def side(S, b_all, lse_row, lse_col, want_dscale):
-                G = torch.empty(S.shape[0], npad, dtype=BF, device=dev)
-                dsp = torch.empty(S.shape[0], dtype=F32, device=dev) if want_dscale else None
-                hip.clip_loss_bwd_g(S, lse_row, lse_col, off, wgt, G, dsp)
-                bt = hip.transpose_bf16(b_all, n, npad)                                        # [E, npad]
-                d = torch.empty(S.shape[0], E, dtype=F32, device=dev)
-                hip.gemm(G, bt, d)                                                             # dA = G @ B_all (scale: below)
-                return d, dsp
-            lse_i_loc, lse_t_loc = sv["lse_loc"][0], sv["lse_loc"][1]
-            lse_i_all, lse_t_all = sv["lse_all"][0], sv["lse_all"][1]
-            dfi, dsp = side(sv["S_i"], sv["allT"], lse_i_loc, lse_t_all, True)
-            dfi *= sv["scale"]                                                                  # d(image features) = scale * G_i @ T_all
-            dft, _ = side(sv["S_t"], sv["allI"], lse_t_loc, lse_i_all, False)                  # allI already carries the scale
-            dscale = hip.colsum(dsp.view(-1, 1))                                               # sum_r sum_j G S
-            if sv["coll"]:
-                dist.all_reduce(dscale)
-            # S already carries the scale: dL/dscale = sum G S / scale; logit_scale = log(scale) => dL/dlogit_scale = sum G S
-            grads["logit_scale"] = dscale.reshape(())
+            if _dfeat is not None:
+                dfi, dft, dls = _dfeat
+                grads["logit_scale"] = dls
+            else:
+                dfi, dft, dscale = _clip_head_bwd(e, sv["S_i"], sv["S_t"], sv["allI"], sv["allT"], sv["lse_loc"], sv["lse_all"],
+                                                  sv["off"], sv["n"], sv["scale"])
+                if sv["coll"]:
+                    dist.all_reduce(dscale)
+                # S already carries the scale: dL/dscale = sum G S / scale; logit_scale = log(scale) => dL/dlogit_scale = sum G S
+                grads["logit_scale"] = dscale.reshape(())
 
             dX = torch.zeros(M, D, dtype=F32, device=dev)
             if e.patch:
@@ -733,6 +730,152 @@ class TrainStep:
         grads["visual.conv1.weight"] = _wgrad_async(dgrid, patch[:Bi * g2], Bi * g2,
                                                     post=lambda d: d[:, :kp].reshape(D, 3, P, P).contiguous())
 
+    # ------------------------------------------------------------------ exact large-batch step over chunks
+    @hip.off_default_stream
+    def accumulate(self, chunks, clone=False, check_features=False):
+        """-> (loss, grads) of ONE contrastive batch made of all the chunks' pairs, computed one chunk at a time; follow it
+        with step(grads).  chunks: a sequence indexed twice, K >= 1 pairs (img, tok), each acceptable to forward() (a staged
+        engine.Captions included); chunk sizes may differ, N = sum of them.
+
+        loss: the symmetric cross-entropy over all N pairs (0-d device tensor): the label of row i of chunk k is
+        (sum of the earlier chunks' sizes) + i, the negatives are all N - 1 other pairs.  grads[key] = d loss / d parameter for
+        every key backward() returns: the true gradient of that loss, no 1 / K factor.  A world of K ranks holding one chunk each
+        would produce 1 / K of it (DDP's mean).  This is NOT the sum of K ordinary steps, whose pairs only compete with the
+        negatives of their own chunk.
+
+        bn="frozen": mathematically the one-shot step on the concatenated batch.  bn="batch": every chunk is normalised with
+        its own batch statistics, as the K ranks of the reference would do; the running statistics are updated once per chunk,
+        in chunk order, and end where K ordinary train-mode forward() calls over the same chunks leave them.
+
+        Two passes (the only exact method that holds one chunk's activations at a time): (1) every chunk through the training
+        forward's arithmetic, nothing kept, running statistics untouched: its gather payload (bf16 hi | lo of the scaled image
+        features / of the text features) goes into a bank [N, 2E] per modality; (2) the head over the bank, one [B_k, N] row
+        block at a time, with the one-shot step's kernels (its rank-sharded path, the bank in place of the all-gather): loss,
+        both global LSE vectors, every chunk's feature gradients; (3) per chunk the saving forward, the backward below the head
+        fed with those feature gradients, and msclip_grad_accumulate into the accumulators.  The features recomputed in (3)
+        equal the banked ones bitwise (every kernel on the path is deterministic); check_features=True compares them and
+        raises on the first chunk that differs.
+
+        LIFETIME: the returned tensors are views of persistent fp32 accumulators owned by this TrainStep (stable addresses:
+        the optimizer table is not rebuilt); they are valid until the next accumulate().  clone=True returns owned copies.
+        K = 1 reproduces forward() + backward() bitwise (token_embedding.weight: atomic scatter-add, to rounding)."""
+        if C.comm.collectives or C.comm.world_size > 1:
+            raise NotImplementedError("TrainStep.accumulate() covers a single process: chunks composed with ranks (world size "
+                                      f"{C.comm.world_size}) are not implemented")
+        K = len(chunks)
+        if K < 1:
+            raise ValueError("TrainStep.accumulate() needs at least one (img, tok) chunk")
+        try:
+            return self._accumulate(chunks, K, clone, check_features)
+        finally:
+            self.eng.force_unfused = False
+
+    def _release_saved(self):
+        sv = getattr(self, "saved", None)
+        if sv is not None:
+            sv["w"].pop("held", None)
+            self.saved = None
+
+    def _feature_pass(self, chunks):
+        """Pass 1 of accumulate(): -> (bank_i, bank_t bf16 [N, 2E], [first row of every chunk] + [N])."""
+        e = self.eng
+        sizes = [int(chunks[k][0].shape[0]) for k in range(len(chunks))]
+        starts = [0]
+        for b in sizes:
+            starts.append(starts[-1] + b)
+        N = starts[-1]
+        bank_i = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
+        bank_t = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
+        for k in range(len(chunks)):
+            img, tok = chunks[k]
+            pi, pt = self._forward(img, tok, head=False, update_stats=False)
+            self._release_saved()                                                # nothing is kept for a backward
+            bank_i[starts[k]:starts[k + 1]] = pi
+            bank_t[starts[k]:starts[k + 1]] = pt
+        return bank_i, bank_t, starts
+
+    def _bank_head(self, bank_i, bank_t, starts):
+        """Pass 2 of accumulate(): -> (loss, [(d image features, d text features, d logit_scale) per chunk])."""
+        e = self.eng
+        dev, E = e.dev, e.E
+        with torch.cuda.device(dev), torch.no_grad():
+            N, K = starts[-1], len(starts) - 1
+            s_dev = e.model.logit_scale.detach().float().exp()
+            a3 = [torch.cat([b[:, :E], b[:, :E], b[:, E:]], dim=1) for b in (bank_i, bank_t)]       # [hi | hi | lo]
+            b3 = [torch.cat([b[:, :E], b[:, E:], b[:, :E]], dim=1) for b in (bank_i, bank_t)]       # [hi | lo | hi]
+            allI, allT = bank_i[:, :E].contiguous(), bank_t[:, :E].contiguous()
+
+            def blocks(k):                                                       # S_i, S_t [B_k, N]: the N x N matrix never exists
+                r0, r1 = starts[k], starts[k + 1]
+                S_i = torch.empty(r1 - r0, N, dtype=F32, device=dev)
+                S_t = torch.empty(r1 - r0, N, dtype=F32, device=dev)
+                hip.gemm(a3[0][r0:r1], b3[1], S_i)
+                hip.gemm(a3[1][r0:r1], b3[0], S_t)
+                return S_i, S_t
+            lse = torch.empty(2, N, dtype=F32, device=dev)
+            parts = torch.empty(K, dtype=F32, device=dev)
+            kept = None
+            for k in range(K):
+                r0, r1 = starts[k], starts[k + 1]
+                S_i, S_t = blocks(k)
+                hip.lse_rows(S_i, lse[0][r0:r1])
+                hip.lse_rows(S_t, lse[1][r0:r1])
+                hip.clip_loss_partial(lse[0][r0:r1], lse[1][r0:r1], S_i, r0, 1.0 / (2.0 * N), parts[k:k + 1])
+                if K == 1:
+                    kept = (S_i, S_t)
+            loss = parts[0].clone() if K == 1 else parts.sum()
+            npad = (N + 63) // 64 * 64
+            bt_T, bt_I = hip.transpose_bf16(allT, N, npad), hip.transpose_bf16(allI, N, npad)
+            dfeat = []
+            for k in range(K):
+                r0, r1 = starts[k], starts[k + 1]
+                S_i, S_t = kept if kept is not None else blocks(k)               # recomputed: the same bits (deterministic GEMM)
+                dfi, dft, dscale = _clip_head_bwd(e, S_i, S_t, allI, allT, lse[:, r0:r1], lse, r0, N, s_dev, bt=(bt_T, bt_I))
+                dfeat.append((dfi, dft, dscale.reshape(())))
+            return loss, dfeat
+
+    def _mark(self, name):
+        """tools/accumulate_bench.py sets self.phase_events = []: a timing event at every phase boundary of accumulate()."""
+        ev_list = getattr(self, "phase_events", None)
+        if ev_list is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(torch.cuda.current_stream(self.eng.dev))
+            ev_list.append((name, ev))
+
+    def _accumulate(self, chunks, K, clone, check_features):
+        e = self.eng
+        self._mark("start")
+        bank_i, bank_t, starts = self._feature_pass(chunks)
+        self._mark("features")
+        loss, dfeat = self._bank_head(bank_i, bank_t, starts)
+        self._mark("head")
+        if not check_features:
+            bank_i = bank_t = None
+        for k in range(K):
+            img, tok = chunks[k]
+            pi, pt = self._forward(img, tok, head=False)
+            if check_features:
+                r0, r1 = starts[k], starts[k + 1]
+                for name, now, banked in (("image", pi, bank_i[r0:r1]), ("text", pt, bank_t[r0:r1])):
+                    if not torch.equal(now, banked):
+                        self._release_saved()
+                        raise RuntimeError(f"TrainStep.accumulate(): the {name} features of chunk {k} recomputed in the gradient "
+                                           "pass differ from the ones the head was computed from (a kernel on the forward path "
+                                           "is not bitwise repeatable)")
+            del pi, pt
+            g = self.backward(_dfeat=dfeat[k])
+            dfeat[k] = None
+            acc = getattr(self, "_acc", None)
+            if acc is None or acc.shapes != {key: (tuple(t.shape), t.device) for key, t in g.items()}:
+                acc = self._acc = _Accumulators(g)
+            with torch.cuda.device(e.dev):
+                self._mark("backward")
+                acc.add(g, 0 if k == 0 else 1)
+                self._mark("accumulate")
+            del g
+        out = acc.views
+        return loss, ({key: t.clone() for key, t in out.items()} if clone else dict(out))
+
     # ------------------------------------------------------------------ optimizer
     def set_epoch(self, epoch):
         """Apply the yaml's learning-rate schedule (self.schedule, train.from_config) for `epoch` to both parameter groups'
@@ -830,6 +973,54 @@ class TrainStep:
             self.eng.repack_after_optimizer()
         else:
             self.eng.refresh(force=True)
+
+
+def _clip_head_bwd(e, S_i, S_t, allI, allT, lse_loc, lse_all, off, n, scale, bt=None):
+    """Backward of the contrastive head for the row blocks S_i / S_t [R, n] (this rank's -- or, in accumulate(), this chunk's --
+    image rows and caption rows, labels off .. off + R): -> (d image features, d text features [R, E] fp32, [1] sum G S =
+    d loss / d logit_scale of these rows).  allI (carries the scale) / allT: the hi parts of all n rows; bt: their transposes
+    (allT^T, allI^T) [E, npad] when the caller already holds them."""
+    dev, E = e.dev, e.E
+    npad = (n + 63) // 64 * 64
+    wgt = 1.0 / (2.0 * n)
+
+    def side(S, b_all, b_t, lse_row, lse_col, want_dscale):
+        G = torch.empty(S.shape[0], npad, dtype=BF, device=dev)
+        dsp = torch.empty(S.shape[0], dtype=F32, device=dev) if want_dscale else None
+        hip.clip_loss_bwd_g(S, lse_row, lse_col, off, wgt, G, dsp)
+        if b_t is None:
+            b_t = hip.transpose_bf16(b_all, n, npad)                                       # [E, npad]
+        d = torch.empty(S.shape[0], E, dtype=F32, device=dev)
+        hip.gemm(G, b_t, d)                                                                # dA = G @ B_all (scale: below)
+        return d, dsp
+    dfi, dsp = side(S_i, allT, bt[0] if bt else None, lse_loc[0], lse_all[1], True)
+    dfi *= scale                                                                            # d(image features) = scale * G_i @ T_all
+    dft, _ = side(S_t, allI, bt[1] if bt else None, lse_loc[1], lse_all[0], False)         # allI already carries the scale
+    return dfi, dft, hip.colsum(dsp.view(-1, 1))                                            # sum_r sum_j G S
+
+
+class _Accumulators:
+    """The persistent fp32 gradient accumulators of TrainStep.accumulate(): one arena, every tensor at a 256-byte boundary,
+    one view per gradient key in the shape backward() returns it; msclip_grad_accumulate's table over them is built once."""
+
+    def __init__(self, grads):
+        self.keys = list(grads)
+        self.shapes = {k: (tuple(t.shape), t.device) for k, t in grads.items()}
+        dev = grads[self.keys[0]].device
+        offs, total = [], 0
+        for k in self.keys:
+            offs.append(total)
+            total += (grads[k].numel() + 63) // 64 * 64
+        self.arena = torch.zeros(total, dtype=F32, device=dev)
+        self.views = {k: self.arena[o:o + grads[k].numel()].view(grads[k].shape) for k, o in zip(self.keys, offs)}
+        self.plan = hip.AccumulatePlan([self.views[k].view(-1) for k in self.keys])
+
+    def add(self, grads, mode):
+        """mode 0: accumulators = grads (the first chunk); 1: += grads.  The few gradients that arrive as permuted views
+        (depthwise adapter weights) are made contiguous first, as _adamw_plan does."""
+        assert len(grads) == len(self.keys)
+        flat = [grads[k] if grads[k].is_contiguous() else grads[k].contiguous() for k in self.keys]
+        self.plan.run(flat, mode)
 
 
 def world_average_(grads):

@@ -1,6 +1,10 @@
 """A few optimizer steps of the MS-CLIP-S training step on synthetic image / caption pairs (random-init weights):
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
+                                    [--accumulate K]
+
+--accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
+TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -27,6 +31,8 @@ def main():
     ap.add_argument("--lr", type=float, default=2e-5)
     ap.add_argument("--steps-per-epoch", type=int, default=0,
                     help="> 0: follow the yaml's TRAIN.LR_SCHEDULER (timm cosine + warm-up, train.CosineSchedule) with this many steps per epoch")
+    ap.add_argument("--accumulate", type=int, default=0,
+                    help="K > 0: one optimizer step per K chunks of --batch pairs (TrainStep.accumulate; single process)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -50,25 +56,34 @@ def main():
     rank = C.comm.rank
     data = [(synth.synth_images(args.batch, seed=1000 * rank + 10 + i).to(dev),
              synth.synth_tokens(args.batch, seed=1000 * rank + 100 + i).to(dev)) for i in range(args.nbatches)]
+    K = args.accumulate
+    if K > 0:                                              # nbatches big batches of K chunks each
+        data = [[(synth.synth_images(args.batch, seed=10 + K * i + k).to(dev), synth.synth_tokens(args.batch, seed=100 + K * i + k).to(dev))
+                 for k in range(K)] for i in range(args.nbatches)]
     losses = []
     for step in range(args.steps):
-        img, tok = data[step % args.nbatches]
+        if K == 0:
+            img, tok = data[step % args.nbatches]
         if args.steps_per_epoch > 0 and step % args.steps_per_epoch == 0:
             ts.set_epoch(step // args.steps_per_epoch)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loss = ts.forward(img, tok)
-        ts.step(ts.backward())
+        if K > 0:
+            loss, grads = ts.accumulate(data[step % args.nbatches])
+            ts.step(grads)
+        else:
+            loss = ts.forward(img, tok)
+            ts.step(ts.backward())
         torch.cuda.synchronize()
         losses.append(float(loss))
         if rank == 0:
             print(f"step {step:3d}  loss {losses[-1]:.4f}  {1e3 * (time.perf_counter() - t0):7.1f} ms", flush=True)
     # the inference-path loss gathers features and all-reduces its partial sums (GATHER_TENSORS: True): EVERY rank runs it,
     # rank 0 prints it
-    inf = float(model.contrastive_loss(*data[0]))
+    inf = float(model.contrastive_loss(*(data[0][0] if K > 0 else data[0])))
     ok = all(l == l for l in losses) and min(losses[-args.nbatches:]) < losses[0]
     if rank == 0:
-        print(f"first batch through the inference path (running statistics): loss {inf:.4f}")
+        print(f"first {'chunk' if K > 0 else 'batch'} through the inference path (running statistics): loss {inf:.4f}")
         print("OK" if ok else "FAILED: the loss did not fall")
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
