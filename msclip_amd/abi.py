@@ -1,5 +1,6 @@
-"""The C ABI as Python binds it, read from include/msclip_hip.h (and, for the later training entry points, from
-include/msclip_hip_train.h under its own version macro): the headers are the only statement of it.
+"""The C ABI as Python binds it, read from include/msclip_hip.h (and, for the later training and optimizer entry points, from
+include/msclip_hip_train.h and include/msclip_hip_optim.h, each under its own version macro): the headers are the only
+statement of it.
 
 The mapping rule, for prototype parameters and struct members alike:
     int -> c_int, float -> c_float, long long -> c_longlong;
@@ -21,6 +22,8 @@ HEADER = os.path.join(_INCLUDE, "msclip_hip.h")
 VERSION_MACRO = "MSCLIP_ABI_VERSION"
 TRAIN_HEADER = os.path.join(_INCLUDE, "msclip_hip_train.h")                # entry points added after msclip_hip.h was frozen
 TRAIN_VERSION_MACRO = "MSCLIP_TRAIN_ABI_VERSION"
+OPTIM_HEADER = os.path.join(_INCLUDE, "msclip_hip_optim.h")                # ... and after msclip_hip_train.h was: gradient clipping
+OPTIM_VERSION_MACRO = "MSCLIP_OPTIM_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "plan.h"
 #include "../../include/msclip_hip.h"
+#include "../../include/msclip_hip_optim.h"
 
 namespace {
 
@@ -742,7 +743,15 @@ struct AdamwBatch {
 };
 static_assert(sizeof(AdamwBatch) <= 4000, "the tensor table travels in the kernel arguments");
 
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2) {
+// CLIP (msclip_adamw_multi_clipped, include/msclip_hip_optim.h): the update sees g[i] * coef[0], the clipping coefficient
+// that msclip_clip_coef left on the device.  The product is ONE fp32 multiply, rounded before the moment updates -- the value
+// torch's clip_grad_norm_ stores back into .grad: the empty asm keeps this file's fast-math from re-associating
+// (1 - b1) * (g * coef) into ((1 - b1) * coef) * g.  CLIP = false is the kernel as it was: coef is not read.
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2,
+                                                          const float* __restrict__ coef_dev) {
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *coef_dev;
   const unsigned e = a.map[blockIdx.x];
   const msclip_adamw_tensor& t = a.t[e & 255u];
   const size_t lo = (size_t)(e >> 8) * AW_CHUNK;
@@ -753,7 +762,13 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, fl
   float* __restrict__ m = t.m + lo;
   float* __restrict__ v = t.v + lo;
   const float lr = t.lr, wd = t.weight_decay;
-  auto upd = [&](float gi, float& mi, float& vi, float& pi) { adamw_update(gi, mi, vi, pi, lr, b1, b2, eps, wd, c1, c2); };
+  auto upd = [&](float gi, float& mi, float& vi, float& pi) {
+    if constexpr (CLIP) {
+      gi *= coef;
+      asm volatile("" : "+v"(gi));
+    }
+    adamw_update(gi, mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
+  };
   // packed copy of the new values (the engine's GEMM operand): same rounding as a cast of the updated tensor
   bf16_t* __restrict__ pkb = t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr;
   float* __restrict__ pkf = t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr;
@@ -1037,9 +1052,9 @@ extern "C" int msclip_adamw(float* p, const float* g, float* m, float* v, long l
   return msclip_launch_status();
 }
 
-extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
-                                  void* stream) {
-  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi);
+template <bool CLIP>
+static int adamw_multi_launch(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                              const float* coef_dev, void* stream) {
   if (!tensors || count < 0 || step < 1) return MSCLIP_EINVAL;
   for (int i = 0; i < count; ++i)
     if (!tensors[i].p || !tensors[i].g || !tensors[i].m || !tensors[i].v || tensors[i].n <= 0 ||
@@ -1049,7 +1064,9 @@ extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count,
   AdamwBatch b;
   int nt = 0, nb = 0;
   auto flush = [&]() {
-    if (nb) hipLaunchKernelGGL(adamw_multi_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2);
+    if (nb)
+      hipLaunchKernelGGL(adamw_multi_kernel<CLIP>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
+                         coef_dev);
     nt = nb = 0;
   };
   for (int i = 0; i < count; ++i) {
@@ -1076,4 +1093,18 @@ extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count,
   }
   flush();
   return msclip_launch_status();
+}
+
+extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                                  void* stream) {
+  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi);
+  return adamw_multi_launch<false>(tensors, count, beta1, beta2, eps, step, nullptr, stream);
+}
+
+// include/msclip_hip_optim.h: `tensors` is a msclip_adamw_tensor[] (void in that header, whose reader knows its own structs only)
+extern "C" int msclip_adamw_multi_clipped(const void* tensors, int count, float beta1, float beta2, float eps, int step,
+                                          const float* coef_dev, void* stream) {
+  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi_clipped);
+  if (!coef_dev || ((size_t)coef_dev & 3)) return MSCLIP_EINVAL;
+  return adamw_multi_launch<true>((const msclip_adamw_tensor*)tensors, count, beta1, beta2, eps, step, coef_dev, stream);
 }

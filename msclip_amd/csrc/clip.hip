@@ -1,0 +1,135 @@
+// Gradient clipping by the global L2 norm (include/msclip_hip_optim.h): the sum of squares of every gradient tensor in a
+// handful of launches, one fp32 partial per 32 K-element chunk, then one workgroup that adds the partials in double and
+// writes {total_norm, coef}.  The clipped AdamW that consumes coef is adamw_multi_kernel<true> (backward.hip).  Streaming,
+// bound by HBM: 4 B per element, one more read of the gradients than the unclipped step.  Fixed addition order, no atomics:
+// bitwise repeatable.  build.sh compiles this file without fast-math (pack.hip's flags): the squares are explicit fmaf, NaN
+// and Inf must travel, and min(1, c) must keep a NaN.
+#include "common.h"
+#include "plan.h"
+#include "../../include/msclip_hip_optim.h"
+
+namespace {
+
+// block b works on chunk (map[b] >> 8) of tensor (map[b] & 255) and writes partials[b]: the chunking of adamw_multi_kernel
+// (backward.hip), the table in the kernel arguments because the gradients' addresses change with every backward.
+// 36 x 16 B + 400 x 4 B of kernel arguments.
+constexpr int SQ_TENSORS = 36, SQ_BLOCKS = 400, SQ_CHUNK = 32768;
+struct SumsqBatch {
+  msclip_sumsq_tensor t[SQ_TENSORS];
+  unsigned map[SQ_BLOCKS];
+};
+static_assert(sizeof(SumsqBatch) <= 4000, "the tensor table travels in the kernel arguments");
+
+// Addition order of a chunk (what the error bound of tests/test_gpu_clip_grad.py counts): a thread keeps one accumulator per
+// float4 component, <= 32 fmaf each, folds them as (x + y) + (z + w), adds at most one head / tail element; six xor-shuffle
+// steps; (w0 + w1) + (w2 + w3) over the four waves.  <= 43 roundings on the path of any term.
+__global__ __launch_bounds__(256) void sumsq_kernel(const SumsqBatch a, float* __restrict__ partials) {
+  const unsigned e = a.map[blockIdx.x];
+  const msclip_sumsq_tensor& t = a.t[e & 255u];
+  const size_t lo = (size_t)(e >> 8) * SQ_CHUNK;
+  const size_t left = (size_t)t.n - lo;
+  const int cnt = left < (size_t)SQ_CHUNK ? (int)left : SQ_CHUNK;
+  const float* __restrict__ g = t.g + lo;
+  // 16-byte body [v0, v1), scalar head [0, v0) and tail [v1, cnt): gradients are views at 4-byte offsets inside the buckets
+  int v0 = (int)(((16 - ((size_t)g & 15)) & 15) >> 2);
+  if (v0 > cnt) v0 = cnt;
+  const int v1 = v0 + ((cnt - v0) & ~3);
+  const int n4 = (v1 - v0) >> 2;
+  const float4* __restrict__ g4 = (const float4*)(g + v0);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int i = threadIdx.x; i < n4; i += 1024) {             // four independent 16-byte loads in flight per lane
+    float4 gv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = i + u * 256;
+      gv[u] = j < n4 ? g4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      s0 = fmaf(gv[u].x, gv[u].x, s0);
+      s1 = fmaf(gv[u].y, gv[u].y, s1);
+      s2 = fmaf(gv[u].z, gv[u].z, s2);
+      s3 = fmaf(gv[u].w, gv[u].w, s3);
+    }
+  }
+  float s = (s0 + s1) + (s2 + s3);
+  const int edge = v0 + (cnt - v1);                          // <= 6 elements
+  if ((int)threadIdx.x < edge) {
+    const int j = (int)threadIdx.x < v0 ? (int)threadIdx.x : v1 + ((int)threadIdx.x - v0);
+    s = fmaf(g[j], g[j], s);
+  }
+  s = wave_sum(s);
+  __shared__ float red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One workgroup: thread t adds partials t, t + 256, ... in double (a serial fp32 fold over the ~4 600 partials of the B/32 model
+// would by itself allow 3e-4 of relative error), then the same tree as above in double.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, long long n, float max_norm,
+                                                        float* __restrict__ out) {
+  double s = 0.0;
+  for (long long i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    const float c = max_norm / (norm + 1e-6f);               // torch: max_norm / (total_norm + 1e-6), clamped to 1 from above
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;                              // (a NaN stays a NaN, as torch.clamp keeps it)
+  }
+}
+
+}  // namespace
+
+extern "C" int msclip_optim_abi_version(void) { return MSCLIP_OPTIM_ABI_VERSION; }
+
+extern "C" int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, float* partials, long long n_partials,
+                                 void* stream) {
+  MSCLIP_PLAN_UNSUPPORTED(msclip_grad_sumsq);
+  if (!tensors || count < 0 || !partials || ((size_t)partials & 3) || n_partials < 0) return MSCLIP_EINVAL;
+  long long need = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!tensors[i].g || tensors[i].n <= 0 || ((size_t)tensors[i].g & 3)) return MSCLIP_EINVAL;
+    need += (tensors[i].n + SQ_CHUNK - 1) / SQ_CHUNK;
+  }
+  if (need != n_partials) return MSCLIP_EINVAL;              // every slot the fold will read is written, none beyond the array
+  SumsqBatch b;
+  int nt = 0, nb = 0;
+  long long base = 0;
+  auto flush = [&]() {
+    if (nb) hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, partials + base);
+    base += nb;
+    nt = nb = 0;
+  };
+  for (int i = 0; i < count; ++i) {
+    const long long chunks = (tensors[i].n + SQ_CHUNK - 1) / SQ_CHUNK;
+    long long c = 0;
+    while (c < chunks) {
+      if (nt == SQ_TENSORS || nb == SQ_BLOCKS) flush();
+      // a tensor that continues in the next launch restarts there at chunk c: shift its base instead of carrying an offset
+      b.t[nt].g = tensors[i].g + c * SQ_CHUNK;
+      b.t[nt].n = tensors[i].n - c * SQ_CHUNK;
+      long long local = 0;
+      while (c < chunks && nb < SQ_BLOCKS) {
+        b.map[nb++] = (unsigned)nt | ((unsigned)local << 8);
+        ++local;
+        ++c;
+      }
+      ++nt;
+    }
+  }
+  flush();
+  return msclip_launch_status();
+}
+
+extern "C" int msclip_clip_coef(const float* partials, long long n, float max_norm, float* out, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_clip_coef, stream, partials, n, max_norm, out);
+  if (!partials || !out || n <= 0 || !(max_norm >= 0.f) || (((size_t)partials | (size_t)out) & 3)) return MSCLIP_EINVAL;
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out);
+  return msclip_launch_status();
+}

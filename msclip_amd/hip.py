@@ -27,6 +27,12 @@ _TRAIN_ABI = abi.load(abi.TRAIN_HEADER, abi.TRAIN_VERSION_MACRO)
 TRAIN_ABI_VERSION = _TRAIN_ABI.version
 TRAIN_EXPORTS = tuple(_TRAIN_ABI.protos)
 AccumTensor = _TRAIN_ABI.structs["msclip_accum_tensor"]
+# include/msclip_hip_optim.h: gradient clipping fused into the AdamW launch, the third table
+_OPTIM_ABI = abi.load(abi.OPTIM_HEADER, abi.OPTIM_VERSION_MACRO)
+OPTIM_ABI_VERSION = _OPTIM_ABI.version
+OPTIM_EXPORTS = tuple(_OPTIM_ABI.protos)
+SumsqTensor = _OPTIM_ABI.structs["msclip_sumsq_tensor"]
+CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
 
 
 class HipUnavailable(RuntimeError):
@@ -55,7 +61,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise HipUnavailable(f"{LIB_PATH} is missing: run msclip_amd/csrc/build.sh (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for header, table in (("msclip_hip.h", _ABI), ("msclip_hip_train.h", _TRAIN_ABI)):
+        for header, table in (("msclip_hip.h", _ABI), ("msclip_hip_train.h", _TRAIN_ABI), ("msclip_hip_optim.h", _OPTIM_ABI)):
             for name, (restype, argtypes) in table.protos.items():         # abi.py states the C type -> ctypes rule
                 fn = getattr(L, name, None)
                 if fn is None:
@@ -68,6 +74,9 @@ def lib():
         if L.msclip_train_abi_version() != TRAIN_ABI_VERSION:
             raise HipUnavailable(f"{LIB_PATH} has training ABI version {L.msclip_train_abi_version()}, this binding needs "
                                  f"{TRAIN_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
+        if L.msclip_optim_abi_version() != OPTIM_ABI_VERSION:
+            raise HipUnavailable(f"{LIB_PATH} has optimizer ABI version {L.msclip_optim_abi_version()}, this binding needs "
+                                 f"{OPTIM_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1713,46 +1722,107 @@ class AdamwPlan:
     training step's parameters, its gradient slots inside the all-reduce buckets and the optimizer state do).
     items: [(p, g, m, v, lr, weight_decay)] or [(p, g, m, v, lr, weight_decay, packed, packed_scale)] of contiguous fp32
     tensors (flat views are fine); `packed` = a bf16 or fp32 tensor of the same element count that receives
-    p_new * packed_scale from the same kernel (the engine's operand copy), or None."""
+    p_new * packed_scale from the same kernel (the engine's operand copy), or None.
 
-    def __init__(self, items):
+    Clipping by the global gradient norm (include/msclip_hip_optim.h; run(..., max_norm=)): the table of msclip_grad_sumsq
+    is derived from this one's (g, n) and set_grads writes both; one partial per 32 K-element chunk lands in `partials`, and
+    `clip` holds {total_norm, coef} on the device.  `joined`: one bool per item, True where an item's tensors ALWAYS start
+    where the previous item's end (the pieces of one parameter that differ in their packed copy): such a run is one entry
+    of the norm's table, so the norm is chunked over whole gradient tensors, as hip.grad_norm chunks them."""
+
+    def __init__(self, items, joined=None):
         n = len(items)
         self.n = n
         self.arr = (AdamwTensor * max(n, 1))()
         self.device = items[0][0].device if n else None
         # parameters, moments and packed copies live as long as the table; the gradients do not (set_grads re-points them)
         self.keep = [(it[0], it[2], it[3]) + tuple(it[6:7]) for it in items]
-        for a, it in zip(self.arr, items):
+        joined = [False] * n if joined is None else list(joined)
+        assert len(joined) == n and not (n and joined[0])
+        self.sq_of = []                                       # per item: its entry of the norm's table, or None inside a run
+        for i, (a, it) in enumerate(zip(self.arr, items)):
             p, g, m, v, lr, wd = it[:6]
             for t in (p, g, m, v):
                 assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() and t.device == p.device
             a.p, a.g, a.m, a.v, a.n, a.lr, a.weight_decay = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, wd
+            if joined[i]:
+                assert a.g == self.arr[i - 1].g + 4 * self.arr[i - 1].n, "a joined item starts where the previous one ends"
+            self.sq_of.append(None if joined[i] else i - sum(joined[:i]))
             pk = it[6] if len(it) > 6 else None
             if pk is not None:
                 assert pk.dtype in (torch.bfloat16, torch.float32) and pk.is_contiguous() and pk.numel() == p.numel() and pk.device == p.device
                 a.pk, a.pk_scale, a.pk_f32 = pk.data_ptr(), float(it[7]), int(pk.dtype == torch.float32)
+        self.n_sq = n - sum(joined)
+        self.sq = (SumsqTensor * max(self.n_sq, 1))()
+        j = -1
+        for a, s in zip(self.arr, self.sq_of):
+            if s is not None:
+                j = s
+                self.sq[j].g, self.sq[j].n = a.g, 0
+            self.sq[j].n += a.n
+        self.n_partials = sum((self.sq[j].n + CLIP_CHUNK - 1) // CLIP_CHUNK for j in range(self.n_sq))
+        # never zeroed: every slot is overwritten by the chunk that owns it, the block by the fold
+        self.partials = torch.empty(max(self.n_partials, 1), dtype=torch.float32, device=self.device) if n else None
+        self.clip = torch.empty(2, dtype=torch.float32, device=self.device) if n else None
+        self.norm, self.coef = (self.clip[0], self.clip[1]) if n else (None, None)      # 0-dim views, written by every clipped run
 
     def set_grads(self, ptrs):
         """Device addresses of this step's gradients, one per item (same element counts as at construction)."""
-        for a, g in zip(self.arr, ptrs):
+        for a, s, g in zip(self.arr, self.sq_of, ptrs):
             a.g = g
+            if s is not None:
+                self.sq[s].g = g
 
     def set_rates(self, rates):
         """rates: [(lr, weight_decay)] per item."""
         for a, (lr, wd) in zip(self.arr, rates):
             a.lr, a.weight_decay = lr, wd
 
-    def run(self, beta1, beta2, eps, step):
+    def run(self, beta1, beta2, eps, step, max_norm=None):
+        """max_norm None: one msclip_adamw_multi call.  Otherwise three calls on the current stream, nothing read back:
+        msclip_grad_sumsq -> msclip_clip_coef (self.clip = {total_norm, coef}) -> msclip_adamw_multi_clipped, the update
+        of torch.nn.utils.clip_grad_norm_(params, max_norm) + AdamW with the gradients left as they are."""
         if not self.n:
             return
         with torch.cuda.device(self.device):
-            _check(lib().msclip_adamw_multi(self.arr, self.n, beta1, beta2, eps, step, _stream()), "msclip_adamw_multi")
+            if max_norm is None:
+                _check(lib().msclip_adamw_multi(self.arr, self.n, beta1, beta2, eps, step, _stream()), "msclip_adamw_multi")
+                return
+            L, st = lib(), _stream()
+            _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
+            _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
+            coef = ctypes.c_void_p(self.clip.data_ptr() + 4)
+            _check(L.msclip_adamw_multi_clipped(self.arr, self.n, beta1, beta2, eps, step, coef, st), "msclip_adamw_multi_clipped")
 
 
 def adamw_multi(items, beta1, beta2, eps, step):
     """items: see AdamwPlan: one msclip_adamw_multi call (a handful of launches for the model's 325 tensors instead of one
     each)."""
     AdamwPlan(items).run(beta1, beta2, eps, step)
+
+
+def grad_norm(tensors, max_norm=None):
+    """Global L2 norm of a list of fp32 tensors (contiguous, any 4-byte-aligned views; empty ones take no part) as the clipped
+    optimizer step computes it (msclip_grad_sumsq + msclip_clip_coef): -> 0-dim device tensor, nothing read back.  With
+    max_norm: -> (norm, coef), coef = min(1, max_norm / (norm + 1e-6))."""
+    live = [t for t in tensors if t.numel() > 0]
+    for t in live:
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.device == live[0].device, (t.dtype, t.device)
+    if not live:
+        raise ValueError("hip.grad_norm() needs at least one non-empty tensor")
+    arr = (SumsqTensor * len(live))()
+    for q, t in zip(arr, live):
+        q.g, q.n = t.data_ptr(), t.numel()
+    n_partials = sum((t.numel() + CLIP_CHUNK - 1) // CLIP_CHUNK for t in live)
+    dev = live[0].device
+    partials = torch.empty(n_partials, dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L, st = lib(), _stream()
+        _check(L.msclip_grad_sumsq(arr, len(live), _p(partials), n_partials, st), "msclip_grad_sumsq")
+        _check(L.msclip_clip_coef(_p(partials), n_partials, 0.0 if max_norm is None else float(max_norm), _p(out), st),
+               "msclip_clip_coef")
+    return out[0] if max_norm is None else (out[0], out[1])
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):

@@ -43,15 +43,21 @@ class TrainStep:
     """forward + backward (+ AdamW step) for one local batch.  `engine` is the model's msclip_amd.engine.Engine."""
 
     def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=1e-8, bn="frozen",
-                 without_wd=("bn", "bias", "ln")):
+                 without_wd=("bn", "bias", "ln"), clip_grad_norm=None):
         """bn = "frozen": BatchNorm with its running statistics (gamma / beta trained; the inference kernels' folded
         form); bn = "batch": train-mode BatchNorm -- per-GPU batch statistics in the forward, their backward, running
         statistics updated with momentum 0.1 (what the reference's modules do in train()).
         Optimizer defaults are the reference yaml's (experiments/model/b32.yaml:39-50: adamW, WD 0.05, no decay on
         'bn' / 'bias' / 'ln'; no OPTIMIZER_ARGS => torch.optim.AdamW's betas (0.9, 0.999) and eps 1e-8).
         `without_wd`: TRAIN.WITHOUT_WD_LIST keywords ('bn': BatchNorm parameters, 'ln': LayerNorm parameters, 'bias': names
-        ending in 'bias')."""
+        ending in 'bias').
+        `clip_grad_norm`: TRAIN.CLIP_GRAD_NORM, the max_norm of torch.nn.utils.clip_grad_norm_ applied inside step(); None, 0
+        and 0.0 mean no clipping (the reference's default, lib/config/default.py:153)."""
         assert bn in ("frozen", "batch")
+        if clip_grad_norm is not None and not float(clip_grad_norm) >= 0.0:
+            raise ValueError(f"clip_grad_norm = {clip_grad_norm!r}: a max_norm >= 0 (or None / 0 for no clipping)")
+        self.clip_grad_norm = clip_grad_norm
+        self.last_grad_norm = self.last_clip_coef = None
         unknown = set(without_wd) - {"bn", "bias", "ln", "gn", "dw"}
         if unknown:
             raise NotImplementedError(f"TRAIN.WITHOUT_WD_LIST keywords {sorted(unknown)} are not implemented")
@@ -944,7 +950,7 @@ class TrainStep:
             for lo, n, pk, scale in dests.get(id(p), [(0, p.numel(), None, 1.0)]):
                 items.append((pf[lo:lo + n], g[lo:lo + n], mf[lo:lo + n], vf[lo:lo + n], lr, wd, pk, scale))
                 pieces.append((k, lo))
-        plan = hip.AdamwPlan(items)
+        plan = hip.AdamwPlan(items, joined=[lo != 0 for _, lo in pieces])     # the norm's table: one entry per gradient tensor
         plan.sig, plan.pieces, plan.names, plan.ngrads = sig, pieces, names, len(grads)
         plan.rates_for = (self.lr, self.lr_share, self.wd, self.wd_share)
         plan.packs = bool(dests)
@@ -957,18 +963,34 @@ class TrainStep:
         """AdamW on the module's fp32 parameters (msclip_adamw_multi), which also writes the engine's bf16 copies of the
         transformer blocks' projections; the engine re-packs the rest (conv side, heads).  backward() already returns
         rank-averaged gradients; world_average=True averages here instead, tensor by tensor (for gradients produced with
-        backward(reduce=False))."""
+        backward(reduce=False)).
+
+        With self.clip_grad_norm set (not None / 0): the step of torch.nn.utils.clip_grad_norm_(parameters, clip_grad_norm,
+        norm_type=2, error_if_nonfinite=False) followed by AdamW, all on the device (include/msclip_hip_optim.h): the L2 norm
+        over every gradient of the dict (one entry per Parameter object, logit_scale included), coef = min(1, max_norm /
+        (norm + 1e-6)), and the optimizer sees g * coef.  Unlike torch, nothing is written back: the gradient dict is left
+        as produced.  Afterwards self.last_grad_norm / self.last_clip_coef are 0-dim device tensors, views of the optimizer
+        table's block that are valid until the next step(); .item() on them is the caller's choice of when to synchronise
+        (step() never does).  A non-finite norm is not skipped: it reaches the parameters as it does in torch.
+        Ranks: the norm is taken after the rank averaging (backward()'s, or world_average=True's), so it is the norm of the
+        averaged gradient, identical on every rank, with no further collective.  After accumulate() it is the norm of the SUM
+        over the chunks, which is what a one-shot step on the whole batch clips."""
         if self.lr is None:
             raise ValueError("TrainStep.step() needs a learning rate: TrainStep(model, lr=...) or train.from_config(model, config)")
         if hasattr(grads, "check_fresh"):
             grads.check_fresh()
         self.steps += 1
+        max_norm = float(self.clip_grad_norm) if self.clip_grad_norm else None
         with torch.no_grad():
             if world_average:
                 world_average_(grads)
             plan = self._adamw_plan(grads)
-            plan.run(self.betas[0], self.betas[1], self.eps, self.steps)
+            plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm)
             plan.hold = None
+        if max_norm is None:
+            self.last_grad_norm = self.last_clip_coef = None
+        else:
+            self.last_grad_norm, self.last_clip_coef = plan.norm, plan.coef
         if plan.packs:
             self.eng.repack_after_optimizer()
         else:
@@ -1119,9 +1141,10 @@ def from_config(model, config, bn="batch"):
     TRAIN.OPTIMIZER (only adamW is implemented: anything else raises), TRAIN.LR / WD / WITHOUT_WD_LIST, TRAIN.OPTIMIZER_ARGS
     (betas / eps; absent => torch.optim.AdamW's defaults, what `AdamW(params, lr=..., weight_decay=..., **{})` gives),
     CUSTOM.LR_SHARE / WD_SHARE for the modality-shared tensors (already scaled with the world size by update_config,
-    lib/config/default.py:299-304).
+    lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off).
     bn = "batch" (default): train-mode BatchNorm as the reference's modules run in train(); "frozen": running statistics."""
     ts = TrainStep(model, bn=bn, **optimizer_settings(config))
+    ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
     ts.schedule = lr_schedule(config)            # TRAIN.LR_SCHEDULER of the yaml (None when the config has none)
     return ts
 

@@ -1,10 +1,13 @@
 """A few optimizer steps of the MS-CLIP-S training step on synthetic image / caption pairs (random-init weights):
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
-                                    [--accumulate K]
+                                    [--accumulate K] [--clip-grad-norm X]
 
 --accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
 TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
+
+--clip-grad-norm X: TRAIN.CLIP_GRAD_NORM, the gradients are clipped to the global L2 norm X inside step() (on the device);
+every fifth step also prints the norm before clipping.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -33,6 +36,8 @@ def main():
                     help="> 0: follow the yaml's TRAIN.LR_SCHEDULER (timm cosine + warm-up, train.CosineSchedule) with this many steps per epoch")
     ap.add_argument("--accumulate", type=int, default=0,
                     help="K > 0: one optimizer step per K chunks of --batch pairs (TrainStep.accumulate; single process)")
+    ap.add_argument("--clip-grad-norm", type=float, default=0.0,
+                    help="X > 0: clip the gradients to the global L2 norm X inside step() (TRAIN.CLIP_GRAD_NORM; 0 = off)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -46,7 +51,7 @@ def main():
     if dist.is_initialized():                              # a process group exists: leave the legacy default stream (once, explicitly)
         from msclip_amd import hip
         hip.use_compute_stream(dev)
-    cfg = named_config(args.model)
+    cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm)])
     from bench import load_schema
     model = get_clip_model(cfg)
     model.load_state_dict(synth.synth_state_dict(load_schema(args.model), seed=0), strict=True)
@@ -76,8 +81,12 @@ def main():
             ts.step(ts.backward())
         torch.cuda.synchronize()
         losses.append(float(loss))
+        ms = 1e3 * (time.perf_counter() - t0)
+        note = ""
+        if ts.last_grad_norm is not None and step % 5 == 0:   # one more read on a step that has just read the loss
+            note = f"  grad norm {ts.last_grad_norm.item():.4g} (clipped to {ts.clip_grad_norm:g})"
         if rank == 0:
-            print(f"step {step:3d}  loss {losses[-1]:.4f}  {1e3 * (time.perf_counter() - t0):7.1f} ms", flush=True)
+            print(f"step {step:3d}  loss {losses[-1]:.4f}  {ms:7.1f} ms{note}", flush=True)
     # the inference-path loss gathers features and all-reduces its partial sums (GATHER_TENSORS: True): EVERY rank runs it,
     # rank 0 prints it
     inf = float(model.contrastive_loss(*(data[0][0] if K > 0 else data[0])))
