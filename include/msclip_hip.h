@@ -581,6 +581,53 @@ int msclip_adamw(float* p, const float* g, float* m, float* v, long long n, floa
 int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
                        void* stream);
 
+/* ---- Gradient clipping by the global L2 norm, fused into the AdamW launch.  The three calls of a clipped step, in stream
+ * order (hip.AdamwPlan.run): msclip_grad_sumsq -> msclip_clip_coef -> msclip_adamw_multi_clipped.  Semantics:
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False) followed by the optimizer, except
+ * that no gradient is rewritten. */
+/* One tensor of msclip_grad_sumsq (host-side array): `n` fp32 elements at `g`, 4-byte aligned. */
+typedef struct msclip_sumsq_tensor {
+  const float* g;
+  long long n;
+} msclip_sumsq_tensor;
+
+/* Sum of squares of `count` tensors in a handful of launches (32 K-element chunks, up to 36 tensors and 400 chunks per
+ * launch, the tensor table travels in the kernel arguments as msclip_adamw_multi's does).  Chunk c of the list (tensors in
+ * table order, a tensor's chunks in address order) writes ONE fp32 partial to partials[c]: the workgroup adds in a fixed
+ * order (per-thread serial sums, wave64 shuffle tree, four waves through LDS), so the result is bitwise repeatable; no
+ * atomics and no zero-fill pass, every slot is overwritten.  16-byte loads where the pointer allows, a scalar head and tail
+ * otherwise.  n_partials must equal sum_i ceil(n_i / 32768).  `tensors` is a HOST array, read before the call returns (so a
+ * plan recording that meets this call is marked unusable). */
+int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, float* partials, long long n_partials, void* stream);
+
+/* out[0] = total_norm = sqrt(sum of the n partials), out[1] = coef = min(1, max_norm / (total_norm + 1e-6)), both fp32.  One
+ * workgroup, the partials added in a fixed order in double.  NaN / Inf in a partial reaches both outputs the way it does in
+ * torch (NaN -> NaN, NaN; Inf -> Inf, 0). */
+int msclip_clip_coef(const float* partials, long long n, float max_norm, float* out, void* stream);
+
+/* msclip_adamw_multi on g[i] * coef_dev[0]: the product is one IEEE fp32 multiply, rounded before the moment updates (the
+ * value torch would have stored back into .grad); g itself is not written.  Everything else, the packed copies included,
+ * is msclip_adamw_multi: with coef 1.0f the results are bitwise the same.  `tensors` is a HOST array, read before the call
+ * returns; coef_dev is a DEVICE pointer, read by the kernels. */
+int msclip_adamw_multi_clipped(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                               const float* coef_dev, void* stream);
+
+/* One tensor of msclip_grad_accumulate (host-side array): `n` fp32 elements of a fresh gradient `g` and of its persistent
+ * accumulator `acc`.  Neither pointer needs more than 4-byte alignment; the two ranges must not overlap. */
+typedef struct msclip_accum_tensor {
+  float* acc;
+  const float* g;
+  long long n;
+} msclip_accum_tensor;
+
+/* Gradient accumulation over the chunks of TrainStep.accumulate, all `count` tensors in a handful of launches (32 K-element
+ * pieces of up to 36 tensors per launch, the tensor table travels in the kernel arguments as msclip_adamw_multi's does).
+ * mode 0: acc[i] = g[i] (the first chunk: no zero-fill pass); mode 1: acc[i] = acc[i] + g[i], one IEEE fp32 add per element
+ * in call order: bitwise torch's acc + g, bitwise repeatable (no atomics).  16-byte accesses wherever acc and g share their
+ * offset within 16 bytes (scalar head and tail around them), 4-byte accesses otherwise.  `tensors` is a HOST array, read
+ * before the call returns (so a plan recording that meets this call is marked unusable). */
+int msclip_grad_accumulate(const msclip_accum_tensor* tensors, int count, int mode, void* stream);
+
 /* ---- Re-packing the convolutional side's derived weights after an optimizer step in ONE launch (msclip_amd/packing.py's folds:
  * eval-mode BatchNorm into the filter, M.py:1825-1861 / 1920-1936; the stem stages' 1x1 shortcut into the 3x3 centre tap; layouts).
  * One item per derived tensor, the table and the per-item first-block table live in DEVICE memory (built once: sources are the
@@ -644,7 +691,7 @@ int msclip_prepare_device(void);
  *   msclip_plan_end -> number of table entries (< 0: unusable).  msclip_plan_abort: give up a recording.
  *   msclip_plan_run(plan, streams, n, ext, n_ext): replay.  Legal under a stream capture whose origin stream is slot 0 provided
  *     every other slot is first touched by a recorded wait on an event of a captured stream (the engine's schedules are).
- *   Entry points that read HOST arrays (msclip_colsum_multi, msclip_adamw_multi) cannot be recorded: the recording fails. */
+ *   Entry points that read HOST arrays (msclip_colsum_multi, msclip_adamw_multi, ...) cannot be recorded: the recording fails. */
 typedef struct msclip_plan_s msclip_plan_s;
 int msclip_plan_create(msclip_plan_s** plan);
 int msclip_plan_destroy(msclip_plan_s* plan);
@@ -682,7 +729,7 @@ int msclip_comm_async_error(void* comm);
 int msclip_allgather_feats(void* comm, const void* send, void* recv, long long count, int dtype, void* stream);
 int msclip_allreduce(void* comm, const void* send, void* recv, long long count, int dtype, int op, void* stream);
 
-#define MSCLIP_ABI_VERSION 8   /* 8 (round 6, late): msclip_gemm_desc.bn_mode / part_rows / bn_consts, msclip_bn_bwd_fused, msclip_stem_conv3x3s2_dual_stats / _norm; 7 (round 6): device-side row counts (M_dev / m_dev / dims), the plan executor, RCCL entry points, msclip_prepare_device; 5-6 (round 5): packed-caption entry points, msclip_qkv_attention / msclip_qkvattn_tables, msclip_pack_weights, single-launch msclip_colsum */
+#define MSCLIP_ABI_VERSION 9   /* 9: msclip_grad_accumulate, msclip_grad_sumsq, msclip_clip_coef, msclip_adamw_multi_clipped and their two structs (no older entry point changed); 8 (round 6, late): msclip_gemm_desc.bn_mode / part_rows / bn_consts, msclip_bn_bwd_fused, msclip_stem_conv3x3s2_dual_stats / _norm; 7 (round 6): device-side row counts (M_dev / m_dev / dims), the plan executor, RCCL entry points, msclip_prepare_device; 5-6 (round 5): packed-caption entry points, msclip_qkv_attention / msclip_qkvattn_tables, msclip_pack_weights, single-launch msclip_colsum */
 int msclip_abi_version(void);
 const char* msclip_build_arch(void);
 

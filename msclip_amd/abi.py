@@ -1,6 +1,4 @@
-"""The C ABI as Python binds it, read from include/msclip_hip.h (and, for the later training and optimizer entry points, from
-include/msclip_hip_train.h and include/msclip_hip_optim.h, each under its own version macro): the headers are the only
-statement of it.
+"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.
 
 The mapping rule, for prototype parameters and struct members alike:
     int -> c_int, float -> c_float, long long -> c_longlong;
@@ -17,13 +15,8 @@ import keyword
 import os
 import re
 
-_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-HEADER = os.path.join(_INCLUDE, "msclip_hip.h")
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "msclip_hip.h")
 VERSION_MACRO = "MSCLIP_ABI_VERSION"
-TRAIN_HEADER = os.path.join(_INCLUDE, "msclip_hip_train.h")                # entry points added after msclip_hip.h was frozen
-TRAIN_VERSION_MACRO = "MSCLIP_TRAIN_ABI_VERSION"
-OPTIM_HEADER = os.path.join(_INCLUDE, "msclip_hip_optim.h")                # ... and after msclip_hip_train.h was: gradient clipping
-OPTIM_VERSION_MACRO = "MSCLIP_OPTIM_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 
@@ -67,12 +60,12 @@ def _members(body, known):
     return fields
 
 
-def parse(text, version_macro=VERSION_MACRO):
-    """Header text -> Abi.  version_macro: the name of the header's `#define <macro> <number>`."""
+def parse(text):
+    """Header text -> Abi."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+" + re.escape(version_macro) + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+" + VERSION_MACRO + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
     if len(version) != 1:
-        raise AbiError(f"expected one '#define {version_macro} <number>', found {len(version)}")
+        raise AbiError(f"expected one '#define {VERSION_MACRO} <number>', found {len(version)}")
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { ... }
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
     structs, protos = {}, {}
@@ -98,6 +91,6 @@ def parse(text, version_macro=VERSION_MACRO):
     return Abi(int(version[0]), {k: v for k, v in structs.items() if v}, protos)
 
 
-def load(path=HEADER, version_macro=VERSION_MACRO):
+def load(path=HEADER):
     with open(path) as f:
-        return parse(f.read(), version_macro)
+        return parse(f.read())

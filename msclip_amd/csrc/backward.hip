@@ -16,7 +16,6 @@
 #include "common.h"
 #include "plan.h"
 #include "../../include/msclip_hip.h"
-#include "../../include/msclip_hip_optim.h"
 
 namespace {
 
@@ -713,101 +712,7 @@ __global__ __launch_bounds__(256) void adapter_grid_vec_kernel(const float* __re
   }
 }
 
-// ---- AdamW (decoupled weight decay), one fused pass per parameter tensor; fp32 states.  One statement of the update with
-// the contractions written out, shared by both kernels: their results are bitwise the same.
-__device__ __forceinline__ void adamw_update(float gi, float& mi, float& vi, float& pi, float lr, float b1, float b2, float eps,
-                                             float wd, float c1, float c2) {
-  mi = __fmaf_rn(b1, mi, (1.f - b1) * gi);
-  vi = __fmaf_rn(b2, vi, (1.f - b2) * gi * gi);
-  const float upd = __fmaf_rn(wd, pi, mi * c1 / (sqrtf(vi * c2) + eps));
-  pi = __fmaf_rn(-lr, upd, pi);
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                                    float wd, float c1, float c2) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float mi = m[i], vi = v[i], pi = p[i];
-    adamw_update(g[i], mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-
-// ---- the same update over many tensors per launch: block b works on chunk (map[b] >> 8) of tensor (map[b] & 255).
-constexpr int AW_TENSORS = 36, AW_BLOCKS = 400, AW_CHUNK = 32768;   // 36 x 64 B + 400 x 4 B of kernel arguments (< 4 KiB)
-struct AdamwBatch {
-  msclip_adamw_tensor t[AW_TENSORS];
-  unsigned map[AW_BLOCKS];
-};
-static_assert(sizeof(AdamwBatch) <= 4000, "the tensor table travels in the kernel arguments");
-
-// CLIP (msclip_adamw_multi_clipped, include/msclip_hip_optim.h): the update sees g[i] * coef[0], the clipping coefficient
-// that msclip_clip_coef left on the device.  The product is ONE fp32 multiply, rounded before the moment updates -- the value
-// torch's clip_grad_norm_ stores back into .grad: the empty asm keeps this file's fast-math from re-associating
-// (1 - b1) * (g * coef) into ((1 - b1) * coef) * g.  CLIP = false is the kernel as it was: coef is not read.
-template <bool CLIP>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2,
-                                                          const float* __restrict__ coef_dev) {
-  float coef = 1.f;
-  if constexpr (CLIP) coef = *coef_dev;
-  const unsigned e = a.map[blockIdx.x];
-  const msclip_adamw_tensor& t = a.t[e & 255u];
-  const size_t lo = (size_t)(e >> 8) * AW_CHUNK;
-  const size_t left = (size_t)t.n - lo;
-  const int cnt = left < (size_t)AW_CHUNK ? (int)left : AW_CHUNK;
-  float* __restrict__ p = t.p + lo;
-  const float* __restrict__ g = t.g + lo;
-  float* __restrict__ m = t.m + lo;
-  float* __restrict__ v = t.v + lo;
-  const float lr = t.lr, wd = t.weight_decay;
-  auto upd = [&](float gi, float& mi, float& vi, float& pi) {
-    if constexpr (CLIP) {
-      gi *= coef;
-      asm volatile("" : "+v"(gi));
-    }
-    adamw_update(gi, mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
-  };
-  // packed copy of the new values (the engine's GEMM operand): same rounding as a cast of the updated tensor
-  bf16_t* __restrict__ pkb = t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr;
-  float* __restrict__ pkf = t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr;
-  const float ps = t.pk_scale;
-  int i0 = 0;
-  if (!(((size_t)p | (size_t)g | (size_t)m | (size_t)v | (size_t)pkf) & 15) && !((size_t)pkb & 7)) {
-    const int n4 = cnt >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      const float4 g4 = ((const float4*)g)[i];
-      float4 m4 = ((float4*)m)[i], v4 = ((float4*)v)[i], p4 = ((float4*)p)[i];
-      upd(g4.x, m4.x, v4.x, p4.x);
-      upd(g4.y, m4.y, v4.y, p4.y);
-      upd(g4.z, m4.z, v4.z, p4.z);
-      upd(g4.w, m4.w, v4.w, p4.w);
-      ((float4*)m)[i] = m4;
-      ((float4*)v)[i] = v4;
-      ((float4*)p)[i] = p4;
-      if (pkb) ((uint2*)pkb)[i] = make_uint2(pack_bf16x2(p4.x * ps, p4.y * ps), pack_bf16x2(p4.z * ps, p4.w * ps));
-      if (pkf) ((float4*)pkf)[i] = make_float4(p4.x * ps, p4.y * ps, p4.z * ps, p4.w * ps);
-    }
-    i0 = n4 << 2;
-  }
-  for (int i = i0 + threadIdx.x; i < cnt; i += 256) {
-    float mi = m[i], vi = v[i], pi = p[i];
-    upd(g[i], mi, vi, pi);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-    if (pkb) pkb[i] = f32_to_bf16(pi * ps);
-    if (pkf) pkf[i] = pi * ps;
-  }
-}
-
 }  // namespace
-
-static int grid_for(size_t n, int per_block, int cap = 4096) {
-  size_t b = (n + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
-}
 
 extern "C" int msclip_transpose_bf16(const void* in, int ldi, void* out, int ldo, int M, int C, int Mpad, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_transpose_bf16, stream, in, ldi, out, ldo, M, C, Mpad);
@@ -853,7 +758,7 @@ extern "C" int msclip_transpose_bf16_multi(const msclip_transpose_item* items_de
 extern "C" int msclip_cast_bf16(const float* x, int ldx, void* y, int ldy, int M, int C, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_cast_bf16, stream, x, ldx, y, ldy, M, C);
   if (!x || !y || M <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldy & 3)) return MSCLIP_EINVAL;
-  hipLaunchKernelGGL(cast_kernel, dim3(grid_for((size_t)M * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
+  hipLaunchKernelGGL(cast_kernel, dim3(grid_for((size_t)M * (C / 4), 256, 4096)), dim3(256), 0, (hipStream_t)stream, x, ldx,
                      (bf16_t*)y, ldy, M, C / 4);
   return msclip_launch_status();
 }
@@ -938,7 +843,7 @@ extern "C" int msclip_colsum(const void* x, int ld, int is_f32, float* out, int 
 extern "C" int msclip_quickgelu(const void* h, void* y, long long n, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_quickgelu, stream, h, y, n);
   if (!h || !y || n <= 0 || (n & 7)) return MSCLIP_EINVAL;
-  hipLaunchKernelGGL(quickgelu_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h,
+  hipLaunchKernelGGL(quickgelu_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h,
                      (bf16_t*)y, (size_t)(n / 8));
   return msclip_launch_status();
 }
@@ -946,7 +851,7 @@ extern "C" int msclip_quickgelu(const void* h, void* y, long long n, void* strea
 extern "C" int msclip_quickgelu_bwd(const void* h, const void* dy, void* dh, long long n, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_quickgelu_bwd, stream, h, dy, dh, n);
   if (!h || !dy || !dh || n <= 0 || (n & 7)) return MSCLIP_EINVAL;
-  hipLaunchKernelGGL(quickgelu_bwd_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h,
+  hipLaunchKernelGGL(quickgelu_bwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h,
                      (const bf16_t*)dy, (bf16_t*)dh, (size_t)(n / 8));
   return msclip_launch_status();
 }
@@ -1040,71 +945,4 @@ extern "C" int msclip_adapter_dx(const float* dsum, int lds, const float* dww, f
     hipLaunchKernelGGL(adapter_dx_kernel, dim3(B * L), dim3(256), 0, (hipStream_t)stream, dsum, lds, dww, dx, lddx, B, L, g, C,
                        usecls);
   return msclip_launch_status();
-}
-
-extern "C" int msclip_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                            float eps, float weight_decay, int step, void* stream) {
-  MSCLIP_PLAN_HOOK(msclip_adamw, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step);
-  if (!p || !g || !m || !v || n <= 0 || step < 1) return MSCLIP_EINVAL;
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for((size_t)n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (size_t)n, lr,
-                     beta1, beta2, eps, weight_decay, c1, c2);
-  return msclip_launch_status();
-}
-
-template <bool CLIP>
-static int adamw_multi_launch(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
-                              const float* coef_dev, void* stream) {
-  if (!tensors || count < 0 || step < 1) return MSCLIP_EINVAL;
-  for (int i = 0; i < count; ++i)
-    if (!tensors[i].p || !tensors[i].g || !tensors[i].m || !tensors[i].v || tensors[i].n <= 0 ||
-        (tensors[i].pk && (tensors[i].pk_f32 < 0 || tensors[i].pk_f32 > 1)))
-      return MSCLIP_EINVAL;
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
-  AdamwBatch b;
-  int nt = 0, nb = 0;
-  auto flush = [&]() {
-    if (nb)
-      hipLaunchKernelGGL(adamw_multi_kernel<CLIP>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                         coef_dev);
-    nt = nb = 0;
-  };
-  for (int i = 0; i < count; ++i) {
-    const long long chunks = (tensors[i].n + AW_CHUNK - 1) / AW_CHUNK;
-    long long c = 0;
-    while (c < chunks) {
-      if (nt == AW_TENSORS || nb == AW_BLOCKS) flush();
-      b.t[nt] = tensors[i];
-      // a tensor that continues in the next launch restarts there at chunk c: shift its base instead of carrying an offset
-      b.t[nt].p += c * AW_CHUNK;
-      b.t[nt].g += c * AW_CHUNK;
-      b.t[nt].m += c * AW_CHUNK;
-      b.t[nt].v += c * AW_CHUNK;
-      b.t[nt].n -= c * AW_CHUNK;
-      if (b.t[nt].pk) b.t[nt].pk = (char*)b.t[nt].pk + (size_t)c * AW_CHUNK * (b.t[nt].pk_f32 ? 4 : 2);
-      long long local = 0;
-      while (c < chunks && nb < AW_BLOCKS) {
-        b.map[nb++] = (unsigned)nt | ((unsigned)local << 8);
-        ++local;
-        ++c;
-      }
-      ++nt;
-    }
-  }
-  flush();
-  return msclip_launch_status();
-}
-
-extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
-                                  void* stream) {
-  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi);
-  return adamw_multi_launch<false>(tensors, count, beta1, beta2, eps, step, nullptr, stream);
-}
-
-// include/msclip_hip_optim.h: `tensors` is a msclip_adamw_tensor[] (void in that header, whose reader knows its own structs only)
-extern "C" int msclip_adamw_multi_clipped(const void* tensors, int count, float beta1, float beta2, float eps, int step,
-                                          const float* coef_dev, void* stream) {
-  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi_clipped);
-  if (!coef_dev || ((size_t)coef_dev & 3)) return MSCLIP_EINVAL;
-  return adamw_multi_launch<true>((const msclip_adamw_tensor*)tensors, count, beta1, beta2, eps, step, coef_dev, stream);
 }

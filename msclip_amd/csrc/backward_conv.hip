@@ -19,11 +19,6 @@
 
 namespace {
 
-static int grid_for(size_t n, int per_block, int cap = 1 << 20) {
-  size_t b = (n + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
-}
-
 // one thread = one (pixel, 8-wide K chunk); grid-stride over pixels*Kp/8
 template <int KIND>   // 0: NHWC bf16 with C % 8 == 0 (vector path), 1: NCHW fp32 image, 2: NCHW bf16 image, 3: NHWC bf16 any C
 __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ xin, bf16_t* __restrict__ col, int B, int H,
@@ -784,7 +779,7 @@ extern "C" int msclip_im2col(const void* x, int x_kind, void* col, int B, int H,
     return MSCLIP_EINVAL;
   if ((Kp % 8) || Kp < KH * KW * C || x_kind < 0 || x_kind > 2) return MSCLIP_EINVAL;
   const size_t total = (size_t)B * Ho * Wo * (Kp / 8);
-  const int grid = grid_for(total, 256);
+  const int grid = grid_for(total, 256, 1 << 20);
   hipStream_t st = (hipStream_t)stream;
   const size_t row_lds = (size_t)C * KH * W * sizeof(float);
   if (x_kind != 0 && row_lds <= 49152 && (long long)B * Ho < (1ll << 31)) {    // the input image: rows through LDS
@@ -835,7 +830,7 @@ extern "C" int msclip_col2im(const void* dcol, int ld, void* dx, int B, int H, i
     return MSCLIP_EINVAL;
   if ((ld % 8) || ld < KH * KW * C || Ho <= 0 || Wo <= 0) return MSCLIP_EINVAL;
   const size_t total = (size_t)B * H * W * (C / 8);
-  hipLaunchKernelGGL(col2im_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcol, ld,
+  hipLaunchKernelGGL(col2im_kernel, dim3(grid_for(total, 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcol, ld,
                      (bf16_t*)dx, B, H, W, C, KH, KW, stride, pad, Ho, Wo, accumulate);
   return msclip_launch_status();
 }
@@ -854,7 +849,7 @@ extern "C" int msclip_dwpool_bwd(const void* dpool, int ldp, const float* w, voi
   if (!dpool || !w || !dtop || B <= 0 || k <= 0 || H <= 0 || H != W || (H % k) || (C % 8) || (ldp % 8) || ldp < C)
     return MSCLIP_EINVAL;
   const size_t total = (size_t)B * H * W * (C / 8);
-  hipLaunchKernelGGL(dwpool_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dpool,
+  hipLaunchKernelGGL(dwpool_bwd_kernel, dim3(grid_for(total, 256, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dpool,
                      ldp, w, (bf16_t*)dtop, B, H, W, C, k, accumulate);
   return msclip_launch_status();
 }

@@ -7,10 +7,11 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffast-math -fno-finite-math-o
 mkdir -p build
 objs=()
 pids=()
-for f in gemm gemm_small attention qkv_attention attention_bwd backward backward_conv rows conv front loss pack api plan comm accumulate clip; do
-  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ gemm_epilogue.h -nt build/$f.o ] || [ plan.h -nt build/$f.o ] || [ ../../include/msclip_hip.h -nt build/$f.o ] || [ ../../include/msclip_hip_train.h -nt build/$f.o ] || [ ../../include/msclip_hip_optim.h -nt build/$f.o ]; then
-    # pack.hip restates tensor algebra that must come out bitwise (IEEE division / square root, no contraction): no fast-math there;
-    # clip.hip's norm and coefficient are compared with torch's and must let NaN / Inf through: the same flags
+for f in gemm gemm_small attention qkv_attention attention_bwd backward backward_conv rows conv front loss pack api plan comm optim clip; do
+  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ gemm_epilogue.h -nt build/$f.o ] || [ plan.h -nt build/$f.o ] || [ multi_tensor.h -nt build/$f.o ] || [ ../../include/msclip_hip.h -nt build/$f.o ]; then
+    # no fast-math for pack.hip (tensor algebra that must come out bitwise: IEEE division / square root, no contraction) and clip.hip
+    # (NaN / Inf must travel), which is why clip.hip is not part of optim.hip: AdamW's division and sqrtf ARE compiled with fast-math,
+    # and moving either across that line changes bits
     if [ $f = pack ] || [ $f = clip ]; then FL="${FLAGS/-ffast-math -fno-finite-math-only/-fno-fast-math -ffp-contract=off}"; else FL="$FLAGS"; fi
     $HIPCC $FL -c $f.hip -o build/$f.o &
     pids+=($!)

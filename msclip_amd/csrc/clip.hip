@@ -1,34 +1,24 @@
-// Gradient clipping by the global L2 norm (include/msclip_hip_optim.h): the sum of squares of every gradient tensor in a
-// handful of launches, one fp32 partial per 32 K-element chunk, then one workgroup that adds the partials in double and
-// writes {total_norm, coef}.  The clipped AdamW that consumes coef is adamw_multi_kernel<true> (backward.hip).  Streaming,
-// bound by HBM: 4 B per element, one more read of the gradients than the unclipped step.  Fixed addition order, no atomics:
-// bitwise repeatable.  build.sh compiles this file without fast-math (pack.hip's flags): the squares are explicit fmaf, NaN
-// and Inf must travel, and min(1, c) must keep a NaN.
+// Gradient clipping by the global L2 norm: the sum of squares of every gradient tensor in a handful of launches, one fp32
+// partial per 32 K-element chunk, then one workgroup that adds the partials in double and writes {total_norm, coef}.  The
+// clipped AdamW that consumes coef is adamw_multi_kernel<true> (optim.hip).  Streaming, bound by HBM: 4 B per element, one
+// more read of the gradients than the unclipped step.  Fixed addition order, no atomics: bitwise repeatable.  build.sh
+// compiles this file without fast-math (pack.hip's flags): the squares are explicit fmaf, NaN and Inf must travel, and
+// min(1, c) must keep a NaN.
 #include "common.h"
+#include "multi_tensor.h"
 #include "plan.h"
-#include "../../include/msclip_hip_optim.h"
+#include "../../include/msclip_hip.h"
 
 namespace {
 
-// block b works on chunk (map[b] >> 8) of tensor (map[b] & 255) and writes partials[b]: the chunking of adamw_multi_kernel
-// (backward.hip), the table in the kernel arguments because the gradients' addresses change with every backward.
-// 36 x 16 B + 400 x 4 B of kernel arguments.
-constexpr int SQ_TENSORS = 36, SQ_BLOCKS = 400, SQ_CHUNK = 32768;
-struct SumsqBatch {
-  msclip_sumsq_tensor t[SQ_TENSORS];
-  unsigned map[SQ_BLOCKS];
-};
-static_assert(sizeof(SumsqBatch) <= 4000, "the tensor table travels in the kernel arguments");
+// block b writes partials[b] (multi_tensor.h); 36 x 16 B + 400 x 4 B of kernel arguments
+using SumsqBatch = MtBatch<msclip_sumsq_tensor, 36, 400>;
 
 // Addition order of a chunk (what the error bound of tests/test_gpu_clip_grad.py counts): a thread keeps one accumulator per
 // float4 component, <= 32 fmaf each, folds them as (x + y) + (z + w), adds at most one head / tail element; six xor-shuffle
 // steps; (w0 + w1) + (w2 + w3) over the four waves.  <= 43 roundings on the path of any term.
 __global__ __launch_bounds__(256) void sumsq_kernel(const SumsqBatch a, float* __restrict__ partials) {
-  const unsigned e = a.map[blockIdx.x];
-  const msclip_sumsq_tensor& t = a.t[e & 255u];
-  const size_t lo = (size_t)(e >> 8) * SQ_CHUNK;
-  const size_t left = (size_t)t.n - lo;
-  const int cnt = left < (size_t)SQ_CHUNK ? (int)left : SQ_CHUNK;
+  MT_DECODE_CHUNK(a, t, lo, cnt);
   const float* __restrict__ g = t.g + lo;
   // 16-byte body [v0, v1), scalar head [0, v0) and tail [v1, cnt): gradients are views at 4-byte offsets inside the buckets
   int v0 = (int)(((16 - ((size_t)g & 15)) & 15) >> 2);
@@ -86,8 +76,6 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
 
 }  // namespace
 
-extern "C" int msclip_optim_abi_version(void) { return MSCLIP_OPTIM_ABI_VERSION; }
-
 extern "C" int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, float* partials, long long n_partials,
                                  void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_grad_sumsq);
@@ -95,35 +83,18 @@ extern "C" int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, 
   long long need = 0;
   for (int i = 0; i < count; ++i) {
     if (!tensors[i].g || tensors[i].n <= 0 || ((size_t)tensors[i].g & 3)) return MSCLIP_EINVAL;
-    need += (tensors[i].n + SQ_CHUNK - 1) / SQ_CHUNK;
+    need += (tensors[i].n + MT_CHUNK - 1) / MT_CHUNK;
   }
   if (need != n_partials) return MSCLIP_EINVAL;              // every slot the fold will read is written, none beyond the array
-  SumsqBatch b;
-  int nt = 0, nb = 0;
-  long long base = 0;
-  auto flush = [&]() {
-    if (nb) hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, partials + base);
-    base += nb;
-    nt = nb = 0;
-  };
-  for (int i = 0; i < count; ++i) {
-    const long long chunks = (tensors[i].n + SQ_CHUNK - 1) / SQ_CHUNK;
-    long long c = 0;
-    while (c < chunks) {
-      if (nt == SQ_TENSORS || nb == SQ_BLOCKS) flush();
-      // a tensor that continues in the next launch restarts there at chunk c: shift its base instead of carrying an offset
-      b.t[nt].g = tensors[i].g + c * SQ_CHUNK;
-      b.t[nt].n = tensors[i].n - c * SQ_CHUNK;
-      long long local = 0;
-      while (c < chunks && nb < SQ_BLOCKS) {
-        b.map[nb++] = (unsigned)nt | ((unsigned)local << 8);
-        ++local;
-        ++c;
-      }
-      ++nt;
-    }
-  }
-  flush();
+  mt_for_each_launch<SumsqBatch>(
+      tensors, count,
+      [](msclip_sumsq_tensor& t, long long k) {
+        t.g += k;
+        t.n -= k;
+      },
+      [&](const SumsqBatch& b, int nb, long long first_chunk) {
+        hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, partials + first_chunk);
+      });
   return msclip_launch_status();
 }
 

@@ -50,6 +50,12 @@ static inline int msclip_launch_status() {
   return hipGetLastError() == hipSuccess ? MSCLIP_OK : MSCLIP_ELAUNCH;
 }
 
+// Workgroups of a grid-stride kernel: ceil(n / per_block), at least 1 and at most cap.
+static inline int grid_for(size_t n, int per_block, int cap) {
+  size_t b = (n + per_block - 1) / per_block;
+  return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t h) {
   return __uint_as_float(((uint32_t)h) << 16);
 }

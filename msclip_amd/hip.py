@@ -19,20 +19,16 @@ INT_MAX = 2 ** 31 - 1
 _ABI = abi.load()                                        # include/msclip_hip.h, read once: the only statement of the C ABI
 ABI_VERSION = _ABI.version
 EXPORTS = tuple(_ABI.protos)
-GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor = (_ABI.structs[n] for n in (
-    "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item", "msclip_transpose_item",
-    "msclip_adamw_tensor"))
-# include/msclip_hip_train.h: the training entry points declared after msclip_hip.h was frozen, in a table of their own
-_TRAIN_ABI = abi.load(abi.TRAIN_HEADER, abi.TRAIN_VERSION_MACRO)
-TRAIN_ABI_VERSION = _TRAIN_ABI.version
-TRAIN_EXPORTS = tuple(_TRAIN_ABI.protos)
-AccumTensor = _TRAIN_ABI.structs["msclip_accum_tensor"]
-# include/msclip_hip_optim.h: gradient clipping fused into the AdamW launch, the third table
-_OPTIM_ABI = abi.load(abi.OPTIM_HEADER, abi.OPTIM_VERSION_MACRO)
-OPTIM_ABI_VERSION = _OPTIM_ABI.version
-OPTIM_EXPORTS = tuple(_OPTIM_ABI.protos)
-SumsqTensor = _OPTIM_ABI.structs["msclip_sumsq_tensor"]
+(GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor, SumsqTensor, AccumTensor) = (
+    _ABI.structs[n] for n in (
+        "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item",
+        "msclip_transpose_item", "msclip_adamw_tensor", "msclip_sumsq_tensor", "msclip_accum_tensor"))
 CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
+
+
+def _n_partials(counts):
+    """Partials that msclip_grad_sumsq writes for tensors of these element counts: one per started chunk of each."""
+    return sum((n + CLIP_CHUNK - 1) // CLIP_CHUNK for n in counts)
 
 
 class HipUnavailable(RuntimeError):
@@ -61,22 +57,15 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise HipUnavailable(f"{LIB_PATH} is missing: run msclip_amd/csrc/build.sh (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for header, table in (("msclip_hip.h", _ABI), ("msclip_hip_train.h", _TRAIN_ABI), ("msclip_hip_optim.h", _OPTIM_ABI)):
-            for name, (restype, argtypes) in table.protos.items():         # abi.py states the C type -> ctypes rule
-                fn = getattr(L, name, None)
-                if fn is None:
-                    raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/{header} declares: rebuild "
-                                         "(bash msclip_amd/csrc/build.sh)")
-                fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in _ABI.protos.items():              # abi.py states the C type -> ctypes rule
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_hip.h declares: rebuild "
+                                     "(bash msclip_amd/csrc/build.sh)")
+            fn.restype, fn.argtypes = restype, argtypes
         if L.msclip_abi_version() != ABI_VERSION:          # a stale build of the library (the struct layouts / entry points moved on)
             raise HipUnavailable(f"{LIB_PATH} has ABI version {L.msclip_abi_version()}, this binding needs {ABI_VERSION}: rebuild "
                                  "(bash msclip_amd/csrc/build.sh)")
-        if L.msclip_train_abi_version() != TRAIN_ABI_VERSION:
-            raise HipUnavailable(f"{LIB_PATH} has training ABI version {L.msclip_train_abi_version()}, this binding needs "
-                                 f"{TRAIN_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
-        if L.msclip_optim_abi_version() != OPTIM_ABI_VERSION:
-            raise HipUnavailable(f"{LIB_PATH} has optimizer ABI version {L.msclip_optim_abi_version()}, this binding needs "
-                                 f"{OPTIM_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1724,7 +1713,7 @@ class AdamwPlan:
     tensors (flat views are fine); `packed` = a bf16 or fp32 tensor of the same element count that receives
     p_new * packed_scale from the same kernel (the engine's operand copy), or None.
 
-    Clipping by the global gradient norm (include/msclip_hip_optim.h; run(..., max_norm=)): the table of msclip_grad_sumsq
+    Clipping by the global gradient norm (run(..., max_norm=)): the table of msclip_grad_sumsq
     is derived from this one's (g, n) and set_grads writes both; one partial per 32 K-element chunk lands in `partials`, and
     `clip` holds {total_norm, coef} on the device.  `joined`: one bool per item, True where an item's tensors ALWAYS start
     where the previous item's end (the pieces of one parameter that differ in their packed copy): such a run is one entry
@@ -1760,7 +1749,7 @@ class AdamwPlan:
                 j = s
                 self.sq[j].g, self.sq[j].n = a.g, 0
             self.sq[j].n += a.n
-        self.n_partials = sum((self.sq[j].n + CLIP_CHUNK - 1) // CLIP_CHUNK for j in range(self.n_sq))
+        self.n_partials = _n_partials(self.sq[j].n for j in range(self.n_sq))
         # never zeroed: every slot is overwritten by the chunk that owns it, the block by the fold
         self.partials = torch.empty(max(self.n_partials, 1), dtype=torch.float32, device=self.device) if n else None
         self.clip = torch.empty(2, dtype=torch.float32, device=self.device) if n else None
@@ -1813,7 +1802,7 @@ def grad_norm(tensors, max_norm=None):
     arr = (SumsqTensor * len(live))()
     for q, t in zip(arr, live):
         q.g, q.n = t.data_ptr(), t.numel()
-    n_partials = sum((t.numel() + CLIP_CHUNK - 1) // CLIP_CHUNK for t in live)
+    n_partials = _n_partials(t.numel() for t in live)
     dev = live[0].device
     partials = torch.empty(n_partials, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
@@ -1833,7 +1822,7 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
 
 
 class AccumulatePlan:
-    """The host-side tensor table of msclip_grad_accumulate (include/msclip_hip_train.h): built once over the persistent fp32
+    """The host-side tensor table of msclip_grad_accumulate: built once over the persistent fp32
     accumulators, per chunk only the gradient addresses are re-pointed.  accs: contiguous fp32 tensors (any 4-byte-aligned
     views); empty ones take no part."""
 

@@ -966,7 +966,7 @@ class TrainStep:
         backward(reduce=False)).
 
         With self.clip_grad_norm set (not None / 0): the step of torch.nn.utils.clip_grad_norm_(parameters, clip_grad_norm,
-        norm_type=2, error_if_nonfinite=False) followed by AdamW, all on the device (include/msclip_hip_optim.h): the L2 norm
+        norm_type=2, error_if_nonfinite=False) followed by AdamW, all on the device: the L2 norm
         over every gradient of the dict (one entry per Parameter object, logit_scale included), coef = min(1, max_norm /
         (norm + 1e-6)), and the optimizer sees g * coef.  Unlike torch, nothing is written back: the gradient dict is left
         as produced.  Afterwards self.last_grad_norm / self.last_clip_coef are 0-dim device tensors, views of the optimizer

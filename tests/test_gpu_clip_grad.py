@@ -1,4 +1,4 @@
-"""Gradient clipping by the global norm on a real MI355X (include/msclip_hip_optim.h): the norm kernels against fp64, the
+"""Gradient clipping by the global norm on a real MI355X: the norm kernels against fp64, the
 clipped AdamW bit for bit against msclip_adamw_multi on gradients that torch multiplied by the device's own coefficient,
 TrainStep(clip_grad_norm=...) on the B/32 and L/14 models, and accumulate() followed by a clipped step.
 

@@ -77,7 +77,8 @@ def _header_text():
 
 def test_library_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(msclip_[a-z0-9_]+)\s*\(", _header_text()))
-    assert declared == set(hip.EXPORTS) and len(hip.EXPORTS) == 103        # EXPORTS is derived from the header (msclip_amd/abi.py)
+    assert declared == set(hip.EXPORTS) and len(hip.EXPORTS) == 107        # EXPORTS is derived from the header (msclip_amd/abi.py)
+    assert sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if re.fullmatch(r"msclip_hip.*\.h", f)) == ["msclip_hip.h"]
     if not os.path.exists(hip.LIB_PATH):
         hip.build()
     lib = ctypes.CDLL(hip.LIB_PATH)
@@ -85,14 +86,14 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     lib.msclip_abi_version.restype = ctypes.c_int
     lib.msclip_build_arch.restype = ctypes.c_char_p
-    assert lib.msclip_abi_version() == hip.ABI_VERSION == 8 and lib.msclip_build_arch() == b"gfx950"
+    assert lib.msclip_abi_version() == hip.ABI_VERSION == 9 and lib.msclip_build_arch() == b"gfx950"
     # struct mirror must match the C layout (6 pointers + 24 ints/floats, then a pointer in the middle)
     assert ctypes.sizeof(hip.GemmDesc) % 8 == 0 and hip.GemmDesc.ktab.offset % 8 == 0
 
 
 _MIRRORS = {"msclip_gemm_desc": "GemmDesc", "msclip_qkvattn_desc": "QkvAttnDesc", "msclip_bn_bwd_side": "BnBwdSide",
             "msclip_fold_item": "FoldItem", "msclip_pack_item": "PackItem", "msclip_transpose_item": "TransposeItem",
-            "msclip_adamw_tensor": "AdamwTensor"}
+            "msclip_adamw_tensor": "AdamwTensor", "msclip_sumsq_tensor": "SumsqTensor", "msclip_accum_tensor": "AccumTensor"}
 
 
 def test_struct_mirrors_match_the_c_compilers_layout(tmp_path):
@@ -121,6 +122,7 @@ def test_struct_mirrors_match_the_c_compilers_layout(tmp_path):
     assert got == expect
     assert "msclip_gemm_desc 280" in got and "msclip_gemm_desc.ktab 112" in got and "msclip_pack_item 144" in got
     assert "msclip_adamw_tensor 64" in got and "msclip_transpose_item.in 0" in got
+    assert "msclip_accum_tensor 24" in got and "msclip_sumsq_tensor 16" in got
 
 
 def test_derived_signatures_are_the_headers():
@@ -142,6 +144,10 @@ def test_derived_signatures_are_the_headers():
         "msclip_plan_run": [vp, pp, ci, pp, ci],
         "msclip_stream_create": [ci, pp],
         "msclip_prepare_device": [],
+        "msclip_grad_accumulate": [vp, ci, ci, vp],
+        "msclip_grad_sumsq": [vp, ci, vp, ll, vp],
+        "msclip_clip_coef": [vp, ll, cf, vp, vp],
+        "msclip_adamw_multi_clipped": [vp, ci, cf, cf, cf, ci, vp, vp],
     }
     for name, args in pinned.items():
         assert protos[name] == (ci, args), name
@@ -149,9 +155,9 @@ def test_derived_signatures_are_the_headers():
     assert [n for n, (res, _) in protos.items() if res is not ci] == ["msclip_gemm_variant", "msclip_plan_op_name", "msclip_build_arch"]
     # every type word of the header is accounted for: counted here from the text, independently of the reader
     text = re.findall(r"\bmsclip_[a-z0-9_]+\s*\(([^)]*)\)", _header_text())
-    assert len(text) == len(protos) == 103
-    assert sum("long long" in t for t in text) == 18 and sum("float" in t for t in text) == 52
-    for word, ctype, count in (("long long", ll, 13), ("float", cf, 17)):                     # ... of them, passed by value
+    assert len(text) == len(protos) == 107
+    assert sum("long long" in t for t in text) == 20 and sum("float" in t for t in text) == 55
+    for word, ctype, count in (("long long", ll, 15), ("float", cf, 19)):                     # ... of them, passed by value
         assert sum(bool(re.search(rf"\b{word}\s+\w", t)) for t in text) == sum(ctype in a for _, a in protos.values()) == count
     assert sum(bool(re.search(r"\*\s*(const\s*)?\*", t)) for t in text) == sum(pp in a for _, a in protos.values()) == 6
     if not os.path.exists(hip.LIB_PATH):
@@ -165,7 +171,7 @@ def test_library_without_a_declared_symbol_is_refused(monkeypatch):
         hip.build()
     monkeypatch.setattr(hip, "_lib", None)
     monkeypatch.setattr(hip, "_ABI", hip._ABI._replace(protos={**hip._ABI.protos, "msclip_not_built": (ctypes.c_int, [])}))
-    with pytest.raises(hip.HipUnavailable, match="msclip_not_built.*rebuild"):
+    with pytest.raises(hip.HipUnavailable, match=r"msclip_not_built.*msclip_hip\.h.*rebuild"):
         hip.lib()
 
 

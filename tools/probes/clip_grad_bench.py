@@ -1,4 +1,4 @@
-"""Cost of gradient clipping inside the optimizer phase (include/msclip_hip_optim.h): HIP events around TrainStep.step() on the
+"""Cost of gradient clipping inside the optimizer phase: HIP events around TrainStep.step() on the
 ViT-B/32 batch-512 training step, alternating unclipped / clipped steps in one process on one GPU.
 
     python tools/probes/clip_grad_bench.py [--model b32-yfcc-msclips] [--batch 512] [--pairs 12] [--bn batch]
