@@ -1,4 +1,5 @@
-"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.
+"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.  The extension header
+include/msclip_ext.h (declarations newer than that header's ABI version) is read by the same rules under its own version macro.
 
 The mapping rule, for prototype parameters and struct members alike:
     int -> c_int, float -> c_float, long long -> c_longlong;
@@ -17,6 +18,9 @@ import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "msclip_hip.h")
 VERSION_MACRO = "MSCLIP_ABI_VERSION"
+# the extension header: declarations newer than msclip_hip.h's ABI version, versioned on their own until they are folded in
+EXT_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext.h")
+EXT_VERSION_MACRO = "MSCLIP_EXT_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 
@@ -60,12 +64,12 @@ def _members(body, known):
     return fields
 
 
-def parse(text):
-    """Header text -> Abi."""
+def parse(text, version_macro=VERSION_MACRO):
+    """Header text -> Abi; `version_macro`: the name of the header's `#define <name> <number>`."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+" + VERSION_MACRO + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+" + re.escape(version_macro) + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
     if len(version) != 1:
-        raise AbiError(f"expected one '#define {VERSION_MACRO} <number>', found {len(version)}")
+        raise AbiError(f"expected one '#define {version_macro} <number>', found {len(version)}")
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { ... }
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
     structs, protos = {}, {}
@@ -91,6 +95,6 @@ def parse(text):
     return Abi(int(version[0]), {k: v for k, v in structs.items() if v}, protos)
 
 
-def load(path=HEADER):
+def load(path=HEADER, version_macro=VERSION_MACRO):
     with open(path) as f:
-        return parse(f.read())
+        return parse(f.read(), version_macro)

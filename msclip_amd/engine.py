@@ -187,6 +187,7 @@ class Engine:
                 # round 5: every derived conv-side tensor rewritten in place by ONE launch (msclip_pack_weights), the two
                 # projection heads by a transposing copy each; everything else the launches read is a view of the parameters
                 plan.run()
+                self.conv_pack = "table"
                 sd = self._sdv
                 self.w_vproj.copy_(sd["visual.proj"].t())
                 self.w_tproj.copy_(sd["text_projection"].t())
@@ -223,6 +224,9 @@ class Engine:
     def _pack(self, m, blocks=True):
         dev = self.dev
         v, vt = m.visual, m.visual.transformer
+        # which statement of the conv side's folds wrote the derived operands last: this tensor algebra, or msclip_pack_weights
+        # ("table", repack_after_optimizer) -- equal to an fp32 ulp, not bitwise (TrainStep.ema_resume restores the same kind)
+        self.conv_pack = "algebra"
         sd = dict(self.state_views())                # a copy: bn_fold_all parks its folds in it
         P.bn_fold_all(sd)
         self.D = m.transformer_width

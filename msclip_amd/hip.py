@@ -23,6 +23,12 @@ EXPORTS = tuple(_ABI.protos)
     _ABI.structs[n] for n in (
         "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item",
         "msclip_transpose_item", "msclip_adamw_tensor", "msclip_sumsq_tensor", "msclip_accum_tensor"))
+# include/msclip_ext.h, the declarations newer than ABI_VERSION (folded into msclip_hip.h by the next ABI clean-up): a second table,
+# so that _ABI / EXPORTS / ABI_VERSION keep describing msclip_hip.h alone
+_EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
+EXT_ABI_VERSION = _EXT.version
+EXT_EXPORTS = tuple(_EXT.protos)
+EmaTensor = _EXT.structs["msclip_ema_tensor"]
 CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
 
 
@@ -66,6 +72,15 @@ def lib():
         if L.msclip_abi_version() != ABI_VERSION:          # a stale build of the library (the struct layouts / entry points moved on)
             raise HipUnavailable(f"{LIB_PATH} has ABI version {L.msclip_abi_version()}, this binding needs {ABI_VERSION}: rebuild "
                                  "(bash msclip_amd/csrc/build.sh)")
+        for name, (restype, argtypes) in _EXT.protos.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext.h declares: rebuild "
+                                     "(bash msclip_amd/csrc/build.sh)")
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.msclip_ext_abi_version() != EXT_ABI_VERSION:
+            raise HipUnavailable(f"{LIB_PATH} has extension ABI version {L.msclip_ext_abi_version()}, this binding needs "
+                                 f"{EXT_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1854,3 +1869,45 @@ class AccumulatePlan:
 def grad_accumulate(accs, grads, mode):
     """One msclip_grad_accumulate call over lists of fp32 tensors (see AccumulatePlan)."""
     AccumulatePlan(accs).run(grads, mode)
+
+
+class EmaPlan:
+    """The host-side tensor table of msclip_ema_multi (include/msclip_ext.h), built once: shadows[i] <- decay * shadows[i] +
+    (1 - decay) * params[i].  Both lists: contiguous fp32 device tensors (any 4-byte-aligned views) of pairwise equal element
+    counts that stay where they are; empty ones take no part.  No two ranges may overlap (not checked)."""
+
+    def __init__(self, shadows, params):
+        assert len(shadows) == len(params), (len(shadows), len(params))
+        for s, p in zip(shadows, params):
+            for t in (s, p):
+                assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.is_contiguous())
+            assert s.numel() == p.numel() and s.device == p.device, (s.numel(), p.numel(), s.device, p.device)
+        self.keep = [(s, p) for s, p in zip(shadows, params) if s.numel() > 0]
+        self.n = len(self.keep)
+        self.arr = (EmaTensor * max(self.n, 1))()
+        self.device = self.keep[0][0].device if self.n else None
+        for a, (s, p) in zip(self.arr, self.keep):
+            assert s.device == self.device
+            a.ema, a.p, a.n = s.data_ptr(), p.data_ptr(), s.numel()
+
+    @staticmethod
+    def coefficients(decay):
+        """-> (decay, 1 - decay) as the kernel gets them: the difference is taken in double and rounded to fp32 once, the
+        scalar that torch's `(1. - decay) * p` multiplies an fp32 tensor by."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"EMA decay = {decay!r}: a value in [0, 1)")
+        return ctypes.c_float(decay).value, ctypes.c_float(1.0 - decay).value
+
+    def run(self, decay):
+        """One msclip_ema_multi call on the current stream."""
+        d, omd = self.coefficients(decay)
+        if not self.n:
+            return
+        with torch.cuda.device(self.device):
+            _check(lib().msclip_ema_multi(self.arr, self.n, d, omd, _stream()), "msclip_ema_multi")
+
+
+def ema_update(shadows, params, decay):
+    """One msclip_ema_multi call over lists of fp32 tensors (see EmaPlan)."""
+    EmaPlan(shadows, params).run(decay)

@@ -43,7 +43,7 @@ class TrainStep:
     """forward + backward (+ AdamW step) for one local batch.  `engine` is the model's msclip_amd.engine.Engine."""
 
     def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=1e-8, bn="frozen",
-                 without_wd=("bn", "bias", "ln"), clip_grad_norm=None):
+                 without_wd=("bn", "bias", "ln"), clip_grad_norm=None, ema_decay=None):
         """bn = "frozen": BatchNorm with its running statistics (gamma / beta trained; the inference kernels' folded
         form); bn = "batch": train-mode BatchNorm -- per-GPU batch statistics in the forward, their backward, running
         statistics updated with momentum 0.1 (what the reference's modules do in train()).
@@ -52,10 +52,17 @@ class TrainStep:
         `without_wd`: TRAIN.WITHOUT_WD_LIST keywords ('bn': BatchNorm parameters, 'ln': LayerNorm parameters, 'bias': names
         ending in 'bias').
         `clip_grad_norm`: TRAIN.CLIP_GRAD_NORM, the max_norm of torch.nn.utils.clip_grad_norm_ applied inside step(); None, 0
-        and 0.0 mean no clipping (the reference's default, lib/config/default.py:153)."""
+        and 0.0 mean no clipping (the reference's default, lib/config/default.py:153).
+        `ema_decay`: TRAIN.EMA_DECAY in [0, 1): fp32 shadow weights (self.ema_shadow, one per entry of named_parameters(),
+        buffers not included) that start as copies of the parameters and follow them on the device after every step(),
+        shadow = decay * shadow + (1 - decay) * parameter; ema_assign() / ema_resume() / ema_weights() put them into the model
+        for evaluation and saving.  None, 0 and 0.0 mean no EMA (the reference's default, lib/config/default.py:146)."""
         assert bn in ("frozen", "batch")
         if clip_grad_norm is not None and not float(clip_grad_norm) >= 0.0:
             raise ValueError(f"clip_grad_norm = {clip_grad_norm!r}: a max_norm >= 0 (or None / 0 for no clipping)")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay = {ema_decay!r}: a decay in [0, 1) (or None / 0 for no EMA)")
+        self.ema_decay = float(ema_decay) if ema_decay else None
         self.clip_grad_norm = clip_grad_norm
         self.last_grad_norm = self.last_clip_coef = None
         unknown = set(without_wd) - {"bn", "bias", "ln", "gn", "dw"}
@@ -75,10 +82,15 @@ class TrainStep:
         self.betas, self.eps = betas, eps
         self.state = {}
         self.steps = 0
+        self._ema = _EmaShadow(model) if self.ema_decay else None
+        self.ema_shadow = self._ema.views if self._ema else None      # {name: fp32 view of the arena}, named_parameters() order
+        self.ema_updates = 0
+        self._ema_assigned = False
 
     # ------------------------------------------------------------------ forward that keeps what the backward needs
     @hip.off_default_stream
     def forward(self, img, tok):
+        self._ema_live("forward")
         try:
             return self._forward(img, tok)
         finally:
@@ -768,6 +780,7 @@ class TrainStep:
         if C.comm.collectives or C.comm.world_size > 1:
             raise NotImplementedError("TrainStep.accumulate() covers a single process: chunks composed with ranks (world size "
                                       f"{C.comm.world_size}) are not implemented")
+        self._ema_live("accumulate")
         K = len(chunks)
         if K < 1:
             raise ValueError("TrainStep.accumulate() needs at least one (img, tok) chunk")
@@ -969,7 +982,9 @@ class TrainStep:
         norm_type=2, error_if_nonfinite=False) followed by AdamW, all on the device: the L2 norm
         over every gradient of the dict (one entry per Parameter object, logit_scale included), coef = min(1, max_norm /
         (norm + 1e-6)), and the optimizer sees g * coef.  Unlike torch, nothing is written back: the gradient dict is left
-        as produced.  Afterwards self.last_grad_norm / self.last_clip_coef are 0-dim device tensors, views of the optimizer
+        as produced.  With ema_decay set, one msclip_ema_multi call follows the optimizer's on the same stream (once per step(),
+        whatever number of chunks accumulate() summed; every rank updates its own shadow from parameters that are identical
+        across ranks: no collective) and self.ema_updates counts it.  Afterwards self.last_grad_norm / self.last_clip_coef are 0-dim device tensors, views of the optimizer
         table's block that are valid until the next step(); .item() on them is the caller's choice of when to synchronise
         (step() never does).  A non-finite norm is not skipped: it reaches the parameters as it does in torch.
         Ranks: the norm is taken after the rank averaging (backward()'s, or world_average=True's), so it is the norm of the
@@ -977,6 +992,7 @@ class TrainStep:
         over the chunks, which is what a one-shot step on the whole batch clips."""
         if self.lr is None:
             raise ValueError("TrainStep.step() needs a learning rate: TrainStep(model, lr=...) or train.from_config(model, config)")
+        self._ema_live("step")
         if hasattr(grads, "check_fresh"):
             grads.check_fresh()
         self.steps += 1
@@ -987,6 +1003,9 @@ class TrainStep:
             plan = self._adamw_plan(grads)
             plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm)
             plan.hold = None
+            if self._ema is not None:                # behind the AdamW launch on the same stream: the shadows follow the new values
+                self._ema.plan.run(self.ema_decay)
+                self.ema_updates += 1
         if max_norm is None:
             self.last_grad_norm = self.last_clip_coef = None
         else:
@@ -995,6 +1014,55 @@ class TrainStep:
             self.eng.repack_after_optimizer()
         else:
             self.eng.refresh(force=True)
+
+
+    # ------------------------------------------------------------------ weight EMA
+    def _ema_live(self, what):
+        if self._ema_assigned:
+            raise RuntimeError(f"TrainStep.{what}() between ema_assign() and ema_resume(): the model holds the shadow weights "
+                               "(evaluate or save, then call ema_resume())")
+
+    @hip.off_default_stream
+    def ema_assign(self):
+        """Put the shadow weights into the model (evaluation, saving): every parameter and its shadow exchange their VALUES in
+        place -- the parameters' addresses are in the optimizer's and the engine's tables, so no storage changes hands --
+        and the engine re-packs.  Until ema_resume() the shadow arena holds the live weights, and step() / forward() /
+        accumulate() / a second ema_assign() raise RuntimeError.  The names follow the reference's unreleased EMA class
+        (lib/utils/utils.py:188-192: shadow, assign, resume)."""
+        if self._ema is None:
+            raise RuntimeError("TrainStep.ema_assign() needs TrainStep(..., ema_decay=...)")
+        self._ema_live("ema_assign")
+        self._ema_conv_pack = self.eng.conv_pack
+        self._ema.swap()
+        self._ema_assigned = True
+        self.eng.refresh(force=True)
+
+    @hip.off_default_stream
+    def ema_resume(self):
+        """Undo ema_assign(): the live weights return to the model bit for bit, the shadows to the arena; the engine re-packs,
+        and where the conv side's operands had last been written by an optimizer step's table-driven re-pack
+        (Engine.repack_after_optimizer: equal to the full pack's to an fp32 ulp, not bitwise) that re-pack runs again, so the
+        engine serves the bits it served before ema_assign()."""
+        if not self._ema_assigned:
+            raise RuntimeError("TrainStep.ema_resume() without an ema_assign() before it")
+        self._ema.swap()
+        self._ema_assigned = False
+        self.eng.refresh(force=True)
+        if self._ema_conv_pack == "table":
+            self.eng.repack_after_optimizer()
+
+    def ema_weights(self):
+        """Context manager: ema_assign() on entry, ema_resume() on exit (also when the body raises)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self.ema_assign()
+            try:
+                yield self
+            finally:
+                self.ema_resume()
+        return scope()
 
 
 def _clip_head_bwd(e, S_i, S_t, allI, allT, lse_loc, lse_all, off, n, scale, bt=None):
@@ -1043,6 +1111,49 @@ class _Accumulators:
         assert len(grads) == len(self.keys)
         flat = [grads[k] if grads[k].is_contiguous() else grads[k].contiguous() for k in self.keys]
         self.plan.run(flat, mode)
+
+
+class _EmaShadow:
+    """The shadow weights of TrainStep(ema_decay=...): one fp32 arena, every tensor at a 256-byte boundary, one view per entry
+    of model.named_parameters() (one per Parameter object: the text-tower aliases of the shared tensors are not separate
+    entries; buffers are not shadowed), each a copy of its parameter at construction.  msclip_ema_multi's table over
+    (shadow, parameter) is built once: neither side moves."""
+
+    def __init__(self, model):
+        named = list(model.named_parameters())
+        dev = named[0][1].device
+        offs, total = [], 0
+        for _, p in named:
+            assert p.dtype == F32 and p.is_contiguous() and p.device == dev, (p.dtype, p.is_contiguous(), p.device)
+            offs.append(total)
+            total += (p.numel() + 63) // 64 * 64
+        with torch.no_grad():
+            self.arena = torch.zeros(total, dtype=F32, device=dev)
+            self.views = {k: self.arena[o:o + p.numel()].view(p.shape) for (k, p), o in zip(named, offs)}
+            self.params = {k: p for k, p in named}
+            for k, p in named:
+                self.views[k].copy_(p.detach())
+        self.plan = hip.EmaPlan([v.view(-1) for v in self.views.values()], [p.data.view(-1) for _, p in named])
+
+    def swap(self):
+        """Exchange the values of every parameter and its shadow, in place on both sides."""
+        with torch.no_grad():
+            for k, p in self.params.items():
+                s = self.views[k]
+                live = p.detach().clone()
+                p.copy_(s)
+                s.copy_(live)
+
+    def load(self, states):
+        """`states`: {name: tensor} of a checkpoint's 'ema_shadow_states', the same names and shapes as the shadows."""
+        if set(states) != set(self.views):
+            odd = sorted(set(states) ^ set(self.views))
+            raise KeyError(f"'ema_shadow_states' does not name this model's parameters (first differences: {odd[:4]})")
+        with torch.no_grad():
+            for k, v in self.views.items():
+                if tuple(states[k].shape) != tuple(v.shape):
+                    raise ValueError(f"'ema_shadow_states'[{k!r}] has shape {tuple(states[k].shape)}, the parameter {tuple(v.shape)}")
+                v.copy_(states[k])
 
 
 def world_average_(grads):
@@ -1108,18 +1219,30 @@ def _optimizer_state_dict(ts):
 
 def save_checkpoint(model, ts, path, step, model_name="", perf=0.0):
     """The reference's resumable checkpoint dict (lib/utils/utils.py:157-200): 'step', 'model', 'state_dict', 'perf',
-    'optimizer'.  Rank 0 only under N > 1."""
+    'optimizer', and with TrainStep(ema_decay=...) 'ema_shadow_states' = {parameter name: CPU tensor}, the reference's
+    `ema_model.shadow` (utils.py:187-188); without EMA the file is what it was before the key existed.  'state_dict' holds the
+    live weights: not to be called between ema_assign() and ema_resume().  Rank 0 only under N > 1."""
+    ts._ema_live("save_checkpoint")
     if not C.comm.is_main_process():
         return
-    torch.save({"step": step + 1, "model": model_name, "perf": perf,
-                "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
-                "optimizer": _optimizer_state_dict(ts)}, path)
+    out = {"step": step + 1, "model": model_name, "perf": perf,
+           "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+           "optimizer": _optimizer_state_dict(ts)}
+    if ts.ema_shadow is not None:
+        out["ema_shadow_states"] = {k: v.detach().cpu() for k, v in ts.ema_shadow.items()}
+    torch.save(out, path)
 
 
 def resume_checkpoint(model, ts, path):
-    """-> the step to continue from.  Loads the module (strict, aliases checked), the AdamW moments and the step count."""
+    """-> the step to continue from.  Loads the module (strict, aliases checked), the AdamW moments and the step count.
+    With TrainStep(ema_decay=...) also the shadow weights from 'ema_shadow_states'; a checkpoint without that key is refused,
+    as the reference asserts (lib/utils/utils.py:129-133).  Without EMA the key is ignored."""
     from .checkpoint import check_aliases, extract_state_dict
+    ts._ema_live("resume_checkpoint")
     obj = torch.load(path, map_location="cpu", weights_only=False)
+    if ts.ema_shadow is not None and "ema_shadow_states" not in obj:
+        raise KeyError(f"{path} has no 'ema_shadow_states': it was written without TRAIN.EMA_DECAY, this TrainStep has "
+                       f"ema_decay = {ts.ema_decay}")
     sd = extract_state_dict(obj)
     model.load_state_dict(sd, strict=True)
     check_aliases(model, sd)
@@ -1131,6 +1254,8 @@ def resume_checkpoint(model, ts, path):
         p = params[names[int(i)]]
         ts.state[names[int(i)]] = (st["exp_avg"].to(p.device).contiguous(), st["exp_avg_sq"].to(p.device).contiguous())
     ts.steps = int(opt["msclip"]["steps"])
+    if ts.ema_shadow is not None:
+        ts._ema.load(obj["ema_shadow_states"])
     ts._plan = None                                   # the cached optimizer table points at the moments just replaced
     ts.eng.refresh(force=True)
     return int(obj.get("step", ts.steps))
@@ -1141,9 +1266,10 @@ def from_config(model, config, bn="batch"):
     TRAIN.OPTIMIZER (only adamW is implemented: anything else raises), TRAIN.LR / WD / WITHOUT_WD_LIST, TRAIN.OPTIMIZER_ARGS
     (betas / eps; absent => torch.optim.AdamW's defaults, what `AdamW(params, lr=..., weight_decay=..., **{})` gives),
     CUSTOM.LR_SHARE / WD_SHARE for the modality-shared tensors (already scaled with the world size by update_config,
-    lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off).
+    lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off), TRAIN.EMA_DECAY
+    (shadow weights updated inside step(); absent or 0.0 = off).
     bn = "batch" (default): train-mode BatchNorm as the reference's modules run in train(); "frozen": running statistics."""
-    ts = TrainStep(model, bn=bn, **optimizer_settings(config))
+    ts = TrainStep(model, bn=bn, ema_decay=ema_setting(config), **optimizer_settings(config))
     ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
     ts.schedule = lr_schedule(config)            # TRAIN.LR_SCHEDULER of the yaml (None when the config has none)
     return ts
@@ -1193,6 +1319,12 @@ def lr_schedule(config):
     return CosineSchedule(epochs=epochs, warmup_epochs=warm,
                           warmup_lr=a.get("warmup_lr", 0.0), min_lr=a.get("min_lr", 0.0),
                           cooldown_epochs=a.get("cooldown_epochs", 0), decay_rate=a.get("decay_rate", 0.1))
+
+
+def ema_setting(config):
+    """TRAIN.EMA_DECAY of a reference config as TrainStep's `ema_decay` (needs no GPU): None when the key is absent or 0.0,
+    the reference's default (lib/config/default.py:146; its run name carries 'ema<decay>' only when > 0, :268-270)."""
+    return float(config.TRAIN.get("EMA_DECAY", 0.0) or 0.0) or None
 
 
 def optimizer_settings(config):

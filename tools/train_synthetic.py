@@ -1,13 +1,16 @@
 """A few optimizer steps of the MS-CLIP-S training step on synthetic image / caption pairs (random-init weights):
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
-                                    [--accumulate K] [--clip-grad-norm X]
+                                    [--accumulate K] [--clip-grad-norm X] [--ema-decay D]
 
 --accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
 TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
 
 --clip-grad-norm X: TRAIN.CLIP_GRAD_NORM, the gradients are clipped to the global L2 norm X inside step() (on the device);
 every fifth step also prints the norm before clipping.
+
+--ema-decay D: TRAIN.EMA_DECAY, shadow weights follow the parameters inside step() (on the device); at the end the
+inference-path loss is also printed under the shadow weights (TrainStep.ema_weights()), next to the live one.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -38,6 +41,8 @@ def main():
                     help="K > 0: one optimizer step per K chunks of --batch pairs (TrainStep.accumulate; single process)")
     ap.add_argument("--clip-grad-norm", type=float, default=0.0,
                     help="X > 0: clip the gradients to the global L2 norm X inside step() (TRAIN.CLIP_GRAD_NORM; 0 = off)")
+    ap.add_argument("--ema-decay", type=float, default=0.0,
+                    help="D in (0, 1): keep an exponential moving average of the weights inside step() (TRAIN.EMA_DECAY; 0 = off)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -51,7 +56,7 @@ def main():
     if dist.is_initialized():                              # a process group exists: leave the legacy default stream (once, explicitly)
         from msclip_amd import hip
         hip.use_compute_stream(dev)
-    cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm)])
+    cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm), "TRAIN.EMA_DECAY", str(args.ema_decay)])
     from bench import load_schema
     model = get_clip_model(cfg)
     model.load_state_dict(synth.synth_state_dict(load_schema(args.model), seed=0), strict=True)
@@ -89,10 +94,16 @@ def main():
             print(f"step {step:3d}  loss {losses[-1]:.4f}  {ms:7.1f} ms{note}", flush=True)
     # the inference-path loss gathers features and all-reduces its partial sums (GATHER_TENSORS: True): EVERY rank runs it,
     # rank 0 prints it
-    inf = float(model.contrastive_loss(*(data[0][0] if K > 0 else data[0])))
+    first = data[0][0] if K > 0 else data[0]
+    inf = float(model.contrastive_loss(*first))
+    ema_inf = None
+    if ts.ema_shadow is not None:
+        with ts.ema_weights():
+            ema_inf = float(model.contrastive_loss(*first))
     ok = all(l == l for l in losses) and min(losses[-args.nbatches:]) < losses[0]
     if rank == 0:
-        print(f"first {'chunk' if K > 0 else 'batch'} through the inference path (running statistics): loss {inf:.4f}")
+        print(f"first {'chunk' if K > 0 else 'batch'} through the inference path (running statistics): loss {inf:.4f}"
+              + (f", under the EMA weights (decay {ts.ema_decay:g}, {ts.ema_updates} updates) {ema_inf:.4f}" if ema_inf is not None else ""))
         print("OK" if ok else "FAILED: the loss did not fall")
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
