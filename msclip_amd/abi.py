@@ -21,6 +21,10 @@ VERSION_MACRO = "MSCLIP_ABI_VERSION"
 # the extension header: declarations newer than msclip_hip.h's ABI version, versioned on their own until they are folded in
 EXT_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext.h")
 EXT_VERSION_MACRO = "MSCLIP_EXT_ABI_VERSION"
+# the second extension header (the row-scale entry points of stochastic depth): its prototypes point to structs of msclip_hip.h,
+# so it is read with those names known (load(..., known=...))
+EXT2_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext2.h")
+EXT2_VERSION_MACRO = "MSCLIP_EXT2_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 
@@ -64,15 +68,16 @@ def _members(body, known):
     return fields
 
 
-def parse(text, version_macro=VERSION_MACRO):
-    """Header text -> Abi; `version_macro`: the name of the header's `#define <name> <number>`."""
+def parse(text, version_macro=VERSION_MACRO, known=()):
+    """Header text -> Abi; `version_macro`: the name of the header's `#define <name> <number>`; `known`: struct names that a
+    header included by this one declares (they may be pointed to; they are not part of the result)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     version = re.findall(r"^[ \t]*#[ \t]*define[ \t]+" + re.escape(version_macro) + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
     if len(version) != 1:
         raise AbiError(f"expected one '#define {version_macro} <number>', found {len(version)}")
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { ... }
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    structs, protos = {}, {}
+    structs, protos = {name: None for name in known}, {}
     for stmt in filter(None, (s.strip() for s in re.split(r";(?![^{}]*\})", text))):      # (a struct body's own `;` do not split)
         struct = _STRUCT.fullmatch(stmt)
         proto = _PROTO.fullmatch(stmt)
@@ -95,6 +100,6 @@ def parse(text, version_macro=VERSION_MACRO):
     return Abi(int(version[0]), {k: v for k, v in structs.items() if v}, protos)
 
 
-def load(path=HEADER, version_macro=VERSION_MACRO):
+def load(path=HEADER, version_macro=VERSION_MACRO, known=()):
     with open(path) as f:
-        return parse(f.read(), version_macro)
+        return parse(f.read(), version_macro, known)

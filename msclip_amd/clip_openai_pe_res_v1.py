@@ -233,6 +233,8 @@ class VisualTransformer(nn.Module):
 class CLIP(nn.Module):
     """M.py:2701-2858 / 2979-3155 for the released MS-CLIP-S configs."""
 
+    drop_path = 0.0      # MODEL.SPEC.VISION.DROP_PATH (get_clip_model sets it): read by train.TrainStep, ignored by inference
+
     def __init__(self, embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size, context_length,
                  vocab_size, transformer_width, transformer_heads, transformer_layers, gather_tensors=False,
                  custom_config=None, precision="bf16"):
@@ -379,16 +381,21 @@ def get_clip_model(config, vocab_size=None, eot_token=None, **kwargs):
     vis, txt = spec.VISION, spec.TEXT
     if vis.MODEL != "vit":
         raise NotImplementedError("ModifiedResNet towers are outside the MS-CLIP-S path")
-    if _get(vis, "DROP_PATH", 0.0):
-        raise NotImplementedError("DROP_PATH > 0 is a training-time feature")
+    # stochastic depth on the vision blocks' residual branches (M.py:3188, 801, 1027-1028): a training-time switch without
+    # parameters -- the module only carries the rate (train.TrainStep reads it); the inference entry points ignore it
+    drop_path = float(_get(vis, "DROP_PATH", 0.0) or 0.0)
+    if not 0.0 <= drop_path < 1.0:
+        raise ValueError(f"MODEL.SPEC.VISION.DROP_PATH = {drop_path!r}: a drop rate in [0, 1)")
     if txt.STYLE != "clip" or txt.TOKENIZER != "clip":
         raise NotImplementedError("only the 'clip' text style/tokenizer is built")
     if _get(spec, "POOL_TYPE", "default") != "default" or _get(spec, "SKIP_CLS", False):
         raise NotImplementedError("POOL_TYPE/SKIP_CLS variants are not part of the released configs")
-    return CLIP(spec.EMBED_DIM, config.TRAIN.IMAGE_SIZE[0], vis.LAYERS, vis.WIDTH, vis.PATCH_SIZE,
-                txt.CONTEXT_LENGTH, vocab_size if vocab_size is not None else txt.VOCAB_SIZE, txt.WIDTH, txt.HEADS,
-                txt.LAYERS, gather_tensors=_get(spec, "GATHER_TENSORS", False), custom_config=config.CUSTOM,
-                precision=_get(spec, "PRECISION", "bf16"))
+    model = CLIP(spec.EMBED_DIM, config.TRAIN.IMAGE_SIZE[0], vis.LAYERS, vis.WIDTH, vis.PATCH_SIZE,
+                 txt.CONTEXT_LENGTH, vocab_size if vocab_size is not None else txt.VOCAB_SIZE, txt.WIDTH, txt.HEADS,
+                 txt.LAYERS, gather_tensors=_get(spec, "GATHER_TENSORS", False), custom_config=config.CUSTOM,
+                 precision=_get(spec, "PRECISION", "bf16"))
+    model.drop_path = drop_path
+    return model
 
 
 build_model = get_clip_model     # the name BASELINE.json's north_star uses; the reference only has get_clip_model

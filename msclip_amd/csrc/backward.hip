@@ -16,6 +16,7 @@
 #include "common.h"
 #include "plan.h"
 #include "../../include/msclip_hip.h"
+#include "../../include/msclip_ext2.h"
 
 namespace {
 
@@ -324,14 +325,19 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ x, 
 // the rows b, b + gridDim.x, ...; thread t the columns 4t .. 4t+3 of every one of them (blockDim.x >= C/4); part[b][C] receives
 // the block's sums (folded by msclip_colsum, fixed order: deterministic).
 __global__ __launch_bounds__(256) void cast_colsum_kernel(const float* __restrict__ x, int ldx, bf16_t* __restrict__ y, int ldy,
-                                                          int M, int C4, float* __restrict__ part, int skip_group) {
+                                                          int M, int C4, float* __restrict__ part, int skip_group,
+                                                          const float* __restrict__ row_scale) {
   const int t = threadIdx.x;
   if (t >= C4) return;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int m = blockIdx.x; m < M; m += gridDim.x) {
     // skip_group g > 0: x holds g + 1 rows per sample, the first of which (the class token) is skipped: output row m reads row m + m / g + 1
     const size_t src = skip_group ? (size_t)m + m / skip_group + 1 : (size_t)m;
-    const float4 v = *(const float4*)(x + src * ldx + t * 4);
+    float4 v = *(const float4*)(x + src * ldx + t * 4);
+    if (row_scale) {                                 // msclip_cast_bf16_colsum_rowscale: copy and sums of row_scale[m] * x
+      const float s = row_scale[m];
+      v.x *= s; v.y *= s; v.z *= s; v.w *= s;
+    }
     uint2 o;
     o.x = pack_bf16x2(v.x, v.y);
     o.y = pack_bf16x2(v.z, v.w);
@@ -388,7 +394,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
                                                      const float* __restrict__ gamma, float* __restrict__ dx, int lddx,
                                                      int accumulate, float* __restrict__ part, int M, float eps,
                                                      bf16_t* __restrict__ dxb, int lddxb, float* __restrict__ sum_part,
-                                                     int sum_accumulate) {
+                                                     int sum_accumulate, const float* __restrict__ row_scale) {
   constexpr int C = 256 * V4;
   __shared__ float red[4][3][C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -420,6 +426,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
   if (m < M) request(m);
   for (; m < M; m += stride) {
     const size_t src = row_idx ? (size_t)row_idx[m] : (size_t)m * row_mul;
+    // msclip_layernorm_bwd_rowscale: the bf16 copy and its column sums carry the row's scale (the branch behind a DropPath), dx does not
+    const float rsc = row_scale ? row_scale[m] : 1.f;
     float4 xv[V4], dv[V4], old[V4];
     float s = 0.f;
 #pragma unroll
@@ -466,6 +474,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
       if (dxb) {
         // the new residual-stream gradient is the NEXT projection's output gradient: its bf16 copy (the operand of that
         // projection's dgrad / wgrad GEMMs) and its column sums (that projection's bias gradient) leave with this pass
+        if (row_scale) { r.x *= rsc; r.y *= rsc; r.z *= rsc; r.w *= rsc; }
         uint2 o;
         o.x = pack_bf16x2(r.x, r.y);
         o.y = pack_bf16x2(r.z, r.w);
@@ -763,16 +772,29 @@ extern "C" int msclip_cast_bf16(const float* x, int ldx, void* y, int ldy, int M
   return msclip_launch_status();
 }
 
-extern "C" int msclip_cast_bf16_colsum(const float* x, int ldx, void* y, int ldy, int M, int C, float* part, int part_blocks,
-                                       int skip_group, void* stream) {
-  MSCLIP_PLAN_HOOK(msclip_cast_bf16_colsum, stream, x, ldx, y, ldy, M, C, part, part_blocks, skip_group);
+static int cast_bf16_colsum_launch(const float* x, int ldx, void* y, int ldy, int M, int C, float* part, int part_blocks,
+                                   int skip_group, const float* row_scale, void* stream) {
   if (!x || !y || !part || M <= 0 || C <= 0 || C > 1024 || (C & 3) || (ldx & 3) || (ldy & 3) || part_blocks < 1 ||
       ((size_t)part & 15) || skip_group < 0 || (skip_group && M % skip_group))
     return MSCLIP_EINVAL;
   hipLaunchKernelGGL(cast_colsum_kernel, dim3(part_blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, (bf16_t*)y, ldy, M, C / 4,
-                     part, skip_group);
+                     part, skip_group, row_scale);
   return msclip_launch_status();
 }
+
+extern "C" int msclip_cast_bf16_colsum(const float* x, int ldx, void* y, int ldy, int M, int C, float* part, int part_blocks,
+                                       int skip_group, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_cast_bf16_colsum, stream, x, ldx, y, ldy, M, C, part, part_blocks, skip_group);
+  return cast_bf16_colsum_launch(x, ldx, y, ldy, M, C, part, part_blocks, skip_group, nullptr, stream);
+}
+
+extern "C" int msclip_cast_bf16_colsum_rowscale(const float* x, int ldx, void* y, int ldy, int M, int C, float* part,
+                                                int part_blocks, int skip_group, const float* row_scale, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_cast_bf16_colsum_rowscale, stream, x, ldx, y, ldy, M, C, part, part_blocks, skip_group, row_scale);
+  return cast_bf16_colsum_launch(x, ldx, y, ldy, M, C, part, part_blocks, skip_group, row_scale, stream);
+}
+
+extern "C" int msclip_ext2_abi_version(void) { return MSCLIP_EXT2_ABI_VERSION; }
 
 // Ticket counters of the single-launch column sums: one ring of 2^18 zero words per device, allocated on first use.
 static bool colsum_two_stage() {
@@ -856,12 +878,12 @@ extern "C" int msclip_quickgelu_bwd(const void* h, const void* dy, void* dh, lon
   return msclip_launch_status();
 }
 
-extern "C" int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx, int row_mul, const void* dy, int lddy,
-                                    int dy_is_f32, const float* gamma, float* dx, int lddx, int accumulate, float* part,
-                                    int part_blocks, int M, int C, float eps, void* dxb, int lddxb, float* sum_part,
-                                    int sum_accumulate, void* stream) {
-  MSCLIP_PLAN_HOOK(msclip_layernorm_bwd, stream, x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps, dxb, lddxb, sum_part, sum_accumulate);
+static int layernorm_bwd_launch(const float* x, int ldx, const int* row_idx, int row_mul, const void* dy, int lddy,
+                                int dy_is_f32, const float* gamma, float* dx, int lddx, int accumulate, float* part,
+                                int part_blocks, int M, int C, float eps, void* dxb, int lddxb, float* sum_part,
+                                int sum_accumulate, const float* row_scale, void* stream) {
   if (!x || !dy || !gamma || !dx || M <= 0 || (C != 512 && C != 768 && C != 1024) || part_blocks < 1) return MSCLIP_EINVAL;
+  if (row_scale && !dxb) return MSCLIP_EINVAL;       // the scale acts on the bf16 copy and its sums only
   // bf16 copy + column sums of the written dx rows: the plain row mapping only (dxb row m = dx row m), both or neither
   if ((dxb != nullptr) != (sum_part != nullptr) || (dxb && (row_idx || row_mul != 1 || (lddxb % 4)))) return MSCLIP_EINVAL;
   int blocks = (M + 3) / 4;
@@ -877,12 +899,30 @@ extern "C" int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx,
   hipStream_t st = (hipStream_t)stream;
 #define LNB(V4, T) hipLaunchKernelGGL((ln_bwd_kernel<V4, T>), dim3(blocks), dim3(256), 0, st, x, ldx, row_idx, row_mul, \
                                       (const T*)dy, lddy, gamma, dx, lddx, accumulate, part, M, eps, (bf16_t*)dxb, lddxb, \
-                                      sum_part, sum_accumulate)
+                                      sum_part, sum_accumulate, row_scale)
   if (C == 768) { if (dy_is_f32) LNB(3, float); else LNB(3, bf16_t); }
   else if (C == 1024) { if (dy_is_f32) LNB(4, float); else LNB(4, bf16_t); }
   else { if (dy_is_f32) LNB(2, float); else LNB(2, bf16_t); }
 #undef LNB
   return msclip_launch_status();
+}
+
+extern "C" int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx, int row_mul, const void* dy, int lddy,
+                                    int dy_is_f32, const float* gamma, float* dx, int lddx, int accumulate, float* part,
+                                    int part_blocks, int M, int C, float eps, void* dxb, int lddxb, float* sum_part,
+                                    int sum_accumulate, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_layernorm_bwd, stream, x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps, dxb, lddxb, sum_part, sum_accumulate);
+  return layernorm_bwd_launch(x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps,
+                              dxb, lddxb, sum_part, sum_accumulate, nullptr, stream);
+}
+
+extern "C" int msclip_layernorm_bwd_rowscale(const float* x, int ldx, const int* row_idx, int row_mul, const void* dy, int lddy,
+                                             int dy_is_f32, const float* gamma, float* dx, int lddx, int accumulate, float* part,
+                                             int part_blocks, int M, int C, float eps, void* dxb, int lddxb, float* sum_part,
+                                             int sum_accumulate, const float* row_scale, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_layernorm_bwd_rowscale, stream, x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps, dxb, lddxb, sum_part, sum_accumulate, row_scale);
+  return layernorm_bwd_launch(x, ldx, row_idx, row_mul, dy, lddy, dy_is_f32, gamma, dx, lddx, accumulate, part, part_blocks, M, C, eps,
+                              dxb, lddxb, sum_part, sum_accumulate, row_scale, stream);
 }
 
 extern "C" int msclip_l2norm_bwd(const float* x, int ldx, const float* dy, int lddy, float* dx, int lddx, int M, int E,

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "plan.h"
 #include "../../include/msclip_hip.h"
+#include "../../include/msclip_ext2.h"
 #include "gemm_epilogue.h"
 
 namespace {
@@ -41,9 +42,13 @@ struct RowSrc {          // per staged X row (conv mode)
 // Interior tile (no guards): transpose the wave's TM x TN 32x32 accumulator tiles through LDS so that 8 lanes
 // cover one 128-byte line of one output row; bias/QuickGELU are applied in accumulator layout, the residual
 // add / ReLU / conversion after the transpose (row-contiguous, full-line residual loads).
-template <int TM, int TN>
+// RS (msclip_gemm_rowscale: resid_kind 1, fp32 out, act 0, host-checked): out = resid + rscale[row] * v, and a row with scale 0
+// leaves as the residual itself.  The table travels in the kernel's COPY of the descriptor, in a member this form cannot use
+// (csum, the LayerNorm fold consumer's): the unscaled instantiations keep their signature and compile to what they were.
+template <int TM, int TN, bool RS = false>
 __device__ __forceinline__ void epilogue_interior(f32x16 (&acc)[TN][TM], const msclip_gemm_desc& a, char* stg,
                                                   int mw0, int nw0, int lane) {
+  const float* __restrict__ rscale = RS ? a.csum : nullptr;
   const int fr = lane & 31, fhi = lane >> 5;
   const int srow = lane >> 3, sch = lane & 7;      // read-back mapping: row i*8 + srow, 16-byte chunk sch
   const float* __restrict__ bias = a.bias;
@@ -106,10 +111,12 @@ __device__ __forceinline__ void epilogue_interior(f32x16 (&acc)[TN][TM], const m
           *(float4*)(wr + ((c ^ wsw) << 4)) = v;
         }
         float4 rv[4];
+        float rs[RS ? 4 : 1];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const size_t row = (size_t)(mrow0 + i * 8 + srow);
           const int n = nw0 + tn * 32 + sch * 4;
+          if constexpr (RS) rs[i] = rscale[row];
           if (n >= a.N) {
             rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
           } else if (a.resid_kind == 1) {
@@ -125,7 +132,13 @@ __device__ __forceinline__ void epilogue_interior(f32x16 (&acc)[TN][TM], const m
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float4 v = *(const float4*)(rd + i * 1024);
-          v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
+          if constexpr (RS) {
+            const float s = rs[i];
+            v.x = s != 0.f ? rv[i].x + s * v.x : rv[i].x; v.y = s != 0.f ? rv[i].y + s * v.y : rv[i].y;
+            v.z = s != 0.f ? rv[i].z + s * v.z : rv[i].z; v.w = s != 0.f ? rv[i].w + s * v.w : rv[i].w;
+          } else {
+            v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
+          }
           if (a.act == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
           const size_t row = (size_t)(mrow0 + i * 8 + srow);
           const int n = nw0 + tn * 32 + sch * 4;
@@ -146,9 +159,10 @@ __device__ __forceinline__ void epilogue_interior(f32x16 (&acc)[TN][TM], const m
 
 // Edge tiles, ragged N, unaligned leading dimensions, row scatter / table residual: guarded, straight from the
 // accumulator layout (lane owns row .. + (lane&31), columns .. + 8g + 4*(lane>>5) + 0..3).
-template <int TM, int TN>
+template <int TM, int TN, bool RS = false>
 __device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const msclip_gemm_desc& a, bool vec, int mw0,
                                                  int nw0, int lane) {
+  const float* __restrict__ rscale = RS ? a.csum : nullptr;
   const int fr = lane & 31, fhi = lane >> 5;
   const float* __restrict__ bias = a.bias;
 #pragma unroll
@@ -159,6 +173,8 @@ __device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const ms
     const size_t orow = (size_t)(m + grp * a.radd + a.roff);
     size_t rrow = (size_t)m;
     if (a.resid_kind == 3) rrow = (size_t)(m - grp * a.rpg + a.roff);
+    float rs = 1.f;
+    if constexpr (RS) rs = rscale[m];                // the launch's row, before the scatter
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
 #pragma unroll
@@ -177,7 +193,11 @@ __device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const ms
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = v[j] / (1.f + __expf(-1.702f * v[j]));
           }
-          if (a.resid_kind == 1 || a.resid_kind == 3) {
+          if constexpr (RS) {
+            const float4 rv = *(const float4*)((const float*)a.resid + rrow * a.ldr + n);
+            v[0] = rs != 0.f ? rv.x + rs * v[0] : rv.x; v[1] = rs != 0.f ? rv.y + rs * v[1] : rv.y;
+            v[2] = rs != 0.f ? rv.z + rs * v[2] : rv.z; v[3] = rs != 0.f ? rv.w + rs * v[3] : rv.w;
+          } else if (a.resid_kind == 1 || a.resid_kind == 3) {
             const float4 rv = *(const float4*)((const float*)a.resid + rrow * a.ldr + n);
             v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
           } else if (a.resid_kind == 2) {
@@ -212,6 +232,10 @@ __device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const ms
             float y = v[j];
             if (bias) y += bias[n + j];
             if (a.act == 1) y = y / (1.f + __expf(-1.702f * y));
+            if constexpr (RS) {
+              const float r = ((const float*)a.resid)[rrow * a.ldr + n + j];
+              y = rs != 0.f ? r + rs * y : r;
+            } else
             if (a.resid_kind == 1 || a.resid_kind == 3) y += ((const float*)a.resid)[rrow * a.ldr + n + j];
             else if (a.resid_kind == 2) y += bf16_to_f32(((const bf16_t*)a.resid)[rrow * a.ldr + n + j]);
             else if (a.resid_kind == 5) y = bf16_to_f32(((const bf16_t*)a.resid)[orow * a.ldr + n + j]) > 0.f ? y : 0.f;
@@ -229,7 +253,7 @@ __device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const ms
 // Tile configuration: BM x BN output tile, WM x WN waves, each wave owns TM x TN 32x32 MFMA tiles.
 //   big  : 256 x 256, 8 waves (2 x 4), 128 KiB LDS, one workgroup per CU  (transformer projections)
 //   small: 128 x 128, 4 waves (2 x 2),  64 KiB LDS, two workgroups per CU (narrow convolutions, tiny heads)
-template <int MODE, int BM, int BN, int WM, int WN>
+template <int MODE, int BM, int BN, int WM, int WN, bool RS = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const msclip_gemm_desc a_in) {
   // Split-K launches (msclip_gemm_splitk): blockIdx.y = K slice; slice s contracts columns [s*K/S, (s+1)*K/S) of both
   // operands into its own fp32 output matrix out[s][M][ldo] (the caller folds the S partials in a fixed order).
@@ -435,9 +459,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const msclip_gemm
 
     // ---- epilogue
     if (vec && plain_rows && cm0 + BM <= a.M && (cn0 + BN <= a.N || !(a.N & 7)))
-      epilogue_interior<TM, TN>(acc, a, (char*)smem[(it + 1) & 1] + wave * STG_BYTES, cm0 + wm, cn0 + wn, lane);
+      epilogue_interior<TM, TN, RS>(acc, a, (char*)smem[(it + 1) & 1] + wave * STG_BYTES, cm0 + wm, cn0 + wn, lane);
     else
-      epilogue_generic<TM, TN>(acc, a, vec, cm0 + wm, cn0 + wn, lane);
+      epilogue_generic<TM, TN, RS>(acc, a, vec, cm0 + wm, cn0 + wn, lane);
   }
 }
 
@@ -521,6 +545,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const msclip_gemm_desc a_i
   static_assert(!(F8 && MODE == 1), "fp8 operands: dense GEMM only");
   static_assert(EPI == 0 || (MODE == 0 && (!F8 || EPI == 2)), "LayerNorm fold: dense GEMM; fp8 operands as the producer only");
   static_assert(EPI != 3 || !F8, "training dgrad epilogue: bf16 operands");
+  static_assert(EPI != 4 || !F8, "row-scaled residual update (msclip_gemm_rowscale; row_scale = its table): bf16 operands");
   static_assert(!TNL || (MODE == 0 && !F8 && EPI == 0), "token-major operands: dense bf16 GEMM, plain epilogues");
   // Split-K launches (msclip_gemm_splitk with tile = 4; the weight gradients of the training step): blockIdx.y = K slice;
   // slice s contracts columns [s*K/S, (s+1)*K/S) of both operands into its own fp32 matrix out[s][M][ldo].  A weight
@@ -986,6 +1011,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const msclip_gemm_desc a_i
         // (a tile lies in one row segment: seg_split % 256 == 0; the second segment's residual stream may sit elsewhere)
         const float* rs = a.resid2 && cm0 >= a.seg_split ? (const float*)a.resid2 : (const float*)a.resid;
         epilogue_rows_stats<TM, TN>(acc, a, stg, cm0 + wm, cn0 + wn, lane_e, bcol, rstat4[0], rstat4[2], rs);
+      } else if constexpr (EPI == 4) {             // fp32 residual update with a per-row scale on the branch (host-checked form)
+        if (vec && plain_rows && cm0 + 256 <= a.M) {
+          if (cn0 + 256 <= a.N) epi_stores = 4 * TM * TN;
+          epilogue_rows<TM, TN, 1, 0, 1, false, true>(acc, a, stg, cm0 + wm, cn0 + wn, lane_e, bcol, row_scale);
+        } else {
+          epilogue_generic16<TM, TN, true>(acc, a, vec, cm0 + wm, cn0 + wn, lane_e, row_scale);
+        }
       } else
       if (vec && plain_rows && cm0 + 256 <= a.M)
       {
@@ -1035,6 +1067,18 @@ static void launch_cfg(const msclip_gemm_desc* d, hipStream_t st, int blocks_per
   const int cap = ncu * blocks_per_cu;
   const int grid = tiles < cap ? tiles : cap;
   hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN>), dim3(grid), dim3(WM * WN * 64), 0, st, *d);
+}
+
+// The generic kernel's row-scaled instantiation (msclip_gemm_rowscale): the table rides in the descriptor copy's csum member.
+template <int BM, int BN, int WM, int WN>
+static void launch_cfg_rowscale(const msclip_gemm_desc* d, hipStream_t st, int blocks_per_cu, const float* rscale) {
+  const int ncu = msclip_device_cus();
+  const int tiles = ((d->M + BM - 1) / BM) * ((d->N + BN - 1) / BN);
+  const int cap = ncu * blocks_per_cu;
+  const int grid = tiles < cap ? tiles : cap;
+  msclip_gemm_desc d2 = *d;
+  d2.csum = rscale;
+  hipLaunchKernelGGL((gemm_kernel<0, BM, BN, WM, WN, true>), dim3(grid), dim3(WM * WN * 64), 0, st, d2);
 }
 
 
@@ -1219,6 +1263,34 @@ extern "C" int msclip_gemm(const msclip_gemm_desc* d, void* stream) {
     case GV_CONV192: launch_cfg<1, 256, 192, 4, 2>(d, st, 1); break;
     case GV_DENSE192: launch_cfg<0, 256, 192, 4, 2>(d, st, 1); break;
     case GV_CONV128: launch_cfg<1, 128, 128, 2, 2>(d, st, 2); break;
+    default: return MSCLIP_EINVAL;
+  }
+  return msclip_launch_status();
+}
+
+// msclip_gemm with a per-row scale on the branch in front of the fp32 residual add (include/msclip_ext2.h): the dense ping-pong
+// kernel's instantiation of its own (EPI 4) or the generic kernels' (RS): the kernels msclip_gemm launches are what they were.
+extern "C" int msclip_gemm_rowscale(const msclip_gemm_desc* d, const float* row_scale, void* stream) {
+  if (!row_scale) return msclip_gemm(d, stream);
+  MSCLIP_PLAN_HOOK(msclip_gemm_rowscale, stream, d, row_scale);
+  const GemmVariant v = pick_variant(d);
+  if (v == GV_INVALID) return MSCLIP_EINVAL;
+  if (d->mode != 0 || d->resid_kind != 1 || !d->resid || d->out_kind != 1 || d->act || d->out2 || d->xb || d->rowstat || d->W2 ||
+      d->part || d->bn_mode || d->resid2)
+    return MSCLIP_EINVAL;
+  if (d->M_dev && v != GV_PP) return MSCLIP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int ncu = device_cus();
+  const int tiles = ((d->M + 255) / 256) * ((d->N + 255) / 256);
+  const int grid = tiles < ncu ? tiles : ncu;
+  switch (v) {
+    case GV_PP: hipLaunchKernelGGL((gemm_pp_kernel<0, false, 4>), dim3(grid), dim3(512), 0, st, *d, row_scale, nullptr); break;
+    case GV_STREAM:                                  // (the streaming kernel carries no row scale: auto falls back, tile 5 is refused)
+      if (d->tile != 0) return MSCLIP_EINVAL;
+      launch_cfg_rowscale<128, 128, 2, 2>(d, st, 2, row_scale);
+      break;
+    case GV_DENSE128: launch_cfg_rowscale<128, 128, 2, 2>(d, st, 2, row_scale); break;
+    case GV_DENSE192: launch_cfg_rowscale<256, 192, 4, 2>(d, st, 1, row_scale); break;
     default: return MSCLIP_EINVAL;
   }
   return msclip_launch_status();

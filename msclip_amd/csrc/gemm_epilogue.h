@@ -85,9 +85,12 @@ __device__ __forceinline__ void bias4_from_bcol(float bcol, int lane, float4 (&b
                : "memory");
 }
 
-template <int TM, int TN, int RK, int ACT, int OUTK, bool TE = false>     // TE: the training-step forms are compiled in
+// RS (msclip_gemm_rowscale; RK 1, fp32 out): out = resid + rscale[row] * (alpha acc + bias) -- the scales of a block's rows are
+// requested with its residual rows (same look-ahead); a row with scale 0 leaves as the residual itself.
+template <int TM, int TN, int RK, int ACT, int OUTK, bool TE = false, bool RS = false>     // TE: the training-step forms are compiled in
 __device__ __forceinline__ void epilogue_rows(f32x4 (&acc)[2 * TN][2 * TM], const msclip_gemm_desc& a, unsigned stg,
-                                              int mw0, int nw0, int lane, float bcol) {
+                                              int mw0, int nw0, int lane, float bcol, const float* __restrict__ rscale = nullptr) {
+  static_assert(!RS || (RK == 1 && ACT == 0 && OUTK == 1), "row scale: the fp32 residual update only");
   float4 bias4[TN];
   bias4_from_bcol<TN>(bcol, lane, bias4);
   // accumulator layout of v_mfma_f32_16x16x32 with swapped operands: acc[ni][mi][r] = C[mi*16 + lane%16][ni*16 + 4*(lane/16) + r]
@@ -102,12 +105,14 @@ __device__ __forceinline__ void epilogue_rows(f32x4 (&acc)[2 * TN][2 * TM], cons
   constexpr int RAHEAD = 2;                                      // residual blocks (32 x 32) requested ahead ...
   constexpr int NRV = RAHEAD;                                    // (the growing look-ahead of epilogue_rows_stats spills here: 129 VGPRs in the standard kernel)
   float4 rv[NRV][4];                                             // raw: fp32 x 4, or bf16 x 4 in .x/.y (unpacked at use)
+  float rsc[RS ? NRV : 1][4];
   auto load_res = [&](int b, float4 (&dst)[4]) {
     const int tm = b / TN, tn = b % TN;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const size_t row = (size_t)(mw0 + tm * 32 + i * 8 + srow);
       const int n = nw0 + tn * 32 + sch * 4;
+      if constexpr (RS) rsc[b % NRV][i] = *(const AS1 float*)(rscale + row);
       if (n >= a.N) {
         dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       } else if (rk == 1) {
@@ -159,7 +164,18 @@ __device__ __forceinline__ void epilogue_rows(f32x4 (&acc)[2 * TN][2 * TM], cons
         v.x = v.x / (1.f + __expf(-1.702f * v.x)); v.y = v.y / (1.f + __expf(-1.702f * v.y));
         v.z = v.z / (1.f + __expf(-1.702f * v.z)); v.w = v.w / (1.f + __expf(-1.702f * v.w));
       }
-      if (rk == 1) {
+      if (RS) {
+        // resid + s * (x + bias) in the ORDER the unscaled instantiation adds its three terms, (resid + bias) + x (this file is
+        // compiled with fast-math, which re-associates the plain form that way): (resid + s bias) + s x as two fused
+        // multiply-adds whose order the empty asm pins, so that s = 1 reproduces the unscaled launch bit for bit
+        // (tests/test_gpu_droppath.py holds the two instantiations to that)
+        const float4 r = rv[b % NRV][i];
+        const float s = rsc[b % NRV][i];
+        float4 u = make_float4(fmaf(s, bias4[tn].x, r.x), fmaf(s, bias4[tn].y, r.y), fmaf(s, bias4[tn].z, r.z), fmaf(s, bias4[tn].w, r.w));
+        asm volatile("" : "+v"(u.x), "+v"(u.y), "+v"(u.z), "+v"(u.w));
+        u = make_float4(fmaf(s, xb[i][0], u.x), fmaf(s, xb[i][1], u.y), fmaf(s, xb[i][2], u.z), fmaf(s, xb[i][3], u.w));
+        v.x = s != 0.f ? u.x : r.x; v.y = s != 0.f ? u.y : r.y; v.z = s != 0.f ? u.z : r.z; v.w = s != 0.f ? u.w : r.w;
+      } else if (rk == 1) {
         const float4 r = rv[b % NRV][i];
         v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
       } else if (TE && rk == 4) {                                    // v *= QuickGELU'(h), h = the bf16 "residual" (training dgrad)
@@ -593,9 +609,10 @@ __device__ __forceinline__ void epilogue_pack8(f32x4 (&acc)[2 * TN][2 * TM], con
 
 // Edge tiles of the ping-pong kernel (rows past M, ragged N, unaligned leading dimensions): guarded, straight from the
 // 16 x 16 accumulator layout (lane owns row mi*16 + lane%16, columns ni*16 + 4*(lane/16) + 0..3).
-template <int TM, int TN>
+// RS: out = resid + rscale[m] * (alpha acc + bias), m the launch's row (resid_kind 1, host-checked).
+template <int TM, int TN, bool RS = false>
 __device__ __forceinline__ void epilogue_generic16(f32x4 (&acc)[2 * TN][2 * TM], const msclip_gemm_desc& a, bool vec,
-                                                   int mw0, int nw0, int lane) {
+                                                   int mw0, int nw0, int lane, const float* __restrict__ rscale = nullptr) {
   const int r16 = lane & 15, quad = lane >> 4;
   const float* __restrict__ bias = a.bias;
 #pragma unroll
@@ -606,6 +623,8 @@ __device__ __forceinline__ void epilogue_generic16(f32x4 (&acc)[2 * TN][2 * TM],
     const size_t orow = (size_t)(m + grp * a.radd + a.roff);       // row scatter (stem -> token rows)
     size_t row = (size_t)m;                                         // residual row
     if (a.resid_kind == 3) row = (size_t)(m - grp * a.rpg + a.roff);
+    float rs = 1.f;
+    if constexpr (RS) rs = rscale[m];
 #pragma unroll
     for (int ni = 0; ni < 2 * TN; ++ni) {
       const int n = nw0 + ni * 16 + quad * 4;
@@ -622,7 +641,11 @@ __device__ __forceinline__ void epilogue_generic16(f32x4 (&acc)[2 * TN][2 * TM],
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = v[j] / (1.f + __expf(-1.702f * v[j]));
         }
-        if (a.resid_kind == 1 || a.resid_kind == 3) {
+        if (RS) {
+          const float4 rv = *(const float4*)((const float*)a.resid + row * a.ldr + n);
+          v[0] = rs != 0.f ? rv.x + rs * v[0] : rv.x; v[1] = rs != 0.f ? rv.y + rs * v[1] : rv.y;
+          v[2] = rs != 0.f ? rv.z + rs * v[2] : rv.z; v[3] = rs != 0.f ? rv.w + rs * v[3] : rv.w;
+        } else if (a.resid_kind == 1 || a.resid_kind == 3) {
           const float4 rv = *(const float4*)((const float*)a.resid + row * a.ldr + n);
           v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
         } else if (a.resid_kind == 2) {
@@ -649,6 +672,10 @@ __device__ __forceinline__ void epilogue_generic16(f32x4 (&acc)[2 * TN][2 * TM],
           float y = v[j];
           if (bias) y += bias[n + j];
           if (a.act == 1) y = y / (1.f + __expf(-1.702f * y));
+          if (RS) {
+            const float r = ((const float*)a.resid)[row * a.ldr + n + j];
+            y = rs != 0.f ? r + rs * y : r;
+          } else
           if (a.resid_kind == 1 || a.resid_kind == 3) y += ((const float*)a.resid)[row * a.ldr + n + j];
           else if (a.resid_kind == 2) y += bf16_to_f32(((const bf16_t*)a.resid)[row * a.ldr + n + j]);
           if (a.act == 2) y = fmaxf(y, 0.f);

@@ -29,6 +29,10 @@ _EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
 EXT_ABI_VERSION = _EXT.version
 EXT_EXPORTS = tuple(_EXT.protos)
 EmaTensor = _EXT.structs["msclip_ema_tensor"]
+# include/msclip_ext2.h: the row-scale entry points (stochastic depth), a third table for the same reason
+_EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
+EXT2_ABI_VERSION = _EXT2.version
+EXT2_EXPORTS = tuple(_EXT2.protos)
 CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
 
 
@@ -81,6 +85,15 @@ def lib():
         if L.msclip_ext_abi_version() != EXT_ABI_VERSION:
             raise HipUnavailable(f"{LIB_PATH} has extension ABI version {L.msclip_ext_abi_version()}, this binding needs "
                                  f"{EXT_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
+        for name, (restype, argtypes) in _EXT2.protos.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext2.h declares: rebuild "
+                                     "(bash msclip_amd/csrc/build.sh)")
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.msclip_ext2_abi_version() != EXT2_ABI_VERSION:
+            raise HipUnavailable(f"{LIB_PATH} has row-scale extension ABI version {L.msclip_ext2_abi_version()}, this binding needs "
+                                 f"{EXT2_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -536,13 +549,15 @@ class FoldOut:
 
 def gemm(x, w, out, *, M=None, bias=None, resid=None, resid_kind=0, act=0, alpha=1.0, conv=None, ktab=None,
          ldx=None, ldo=None, ldr=None, rpg=INT_MAX, radd=0, roff=0, N=None, tile=0, out2=None, fold_in=None, fold_out=None,
-         colsum_part=None, mdev=None, bn_stats_part=None, bn_consts=None):
+         colsum_part=None, mdev=None, bn_stats_part=None, bn_consts=None, row_scale=None):
     """out = epilogue(alpha * x @ w^T).  x: bf16 [M, K] (or NHWC activation when conv=(H, W, Cin, Ho, Wo, stride, pad)),
     w: bf16 [N, Kpad]; out: bf16 or fp32 2-D buffer.  Training-step forms (ping-pong kernel): out2 = second bf16 output that
     receives the value before the activation; resid_kind = RESID_GELUGRAD multiplies by QuickGELU'(resid) (resid bf16) and,
     with colsum_part (fp32 [M / 128, N]), also leaves the column sums of every 128 stored rows there.
     mdev: a 1-element int32 device tensor; the kernel runs min(M, mdev[0]) rows (msclip_gemm_desc.M_dev: packed captions whose row
-    count never visits the host; M -- x's row count -- is the bound the launch is sized for)."""
+    count never visits the host; M -- x's row count -- is the bound the launch is sized for).
+    row_scale (fp32 [>= M], msclip_gemm_rowscale; needs resid_kind RESID_F32, an fp32 out, no activation):
+    out = resid + row_scale[m] * (alpha * x @ w^T + bias) -- the residual branch behind a DropPath; None: plain msclip_gemm."""
     _bf16(w)
     d = GemmDesc()
     d.X, d.W, d.zero, d.out = x.data_ptr(), w.data_ptr(), zero_page(x.device).data_ptr(), out.data_ptr()
@@ -609,6 +624,12 @@ def gemm(x, w, out, *, M=None, bias=None, resid=None, resid_kind=0, act=0, alpha
         _f32(bn_consts)
         assert bn_consts.is_contiguous() and tuple(bn_consts.shape) == (5, d.N) and out2 is not None and bias is None
         d.bn_mode, d.bn_consts = 2, bn_consts.data_ptr()
+    if row_scale is not None:
+        _f32(row_scale)
+        assert row_scale.numel() >= d.M and row_scale.device == x.device
+        launch, what = (lambda: lib().msclip_gemm_rowscale(ctypes.byref(d), _p(row_scale), _stream())), "msclip_gemm_rowscale"
+    else:
+        launch, what = (lambda: lib().msclip_gemm(ctypes.byref(d), _stream())), "msclip_gemm"
     probe = (_gemm_probe.get(d.mode) or _gemm_probe.get(gemm_variant(d))) if _gemm_probe else None
     rec = _REC[0]
     if probe is not None or rec is not None:
@@ -627,10 +648,10 @@ def gemm(x, w, out, *, M=None, bias=None, resid=None, resid_kind=0, act=0, alpha
             rec.note("gemm:" + gemm_variant(d), flops, tag, nbytes, mdev, d.M)
         if probe is not None:
             t0 = probe.begin()
-            _check(lib().msclip_gemm(ctypes.byref(d), _stream()), "msclip_gemm")
+            _check(launch(), what)
             probe.end(t0, flops, tag, nbytes, rows=(mdev, d.M))
             return out
-    _check(lib().msclip_gemm(ctypes.byref(d), _stream()), "msclip_gemm")
+    _check(launch(), what)
     return out
 
 
@@ -1106,9 +1127,12 @@ def cast_bf16(x, out=None):
     return out
 
 
-def cast_bf16_colsum(x, out=None, fold=True, skip_group=0):
+def cast_bf16_colsum(x, out=None, fold=True, skip_group=0, row_scale=None, blocks=None):
     """-> (bf16 copy of the fp32 matrix x, its column sums fp32 [C]) from one pass over x (fold=False: the per-block partial sums
-    [blocks, C] instead, for a FoldPlan)."""
+    [blocks, C] instead, for a FoldPlan).  row_scale (fp32 [M], msclip_cast_bf16_colsum_rowscale): copy and sums of
+    row_scale[m] * x[m] instead; x is not written.  blocks: the number of partial-sum rows (default: one per 16 rows, at most 1024);
+    blocks = M makes every partial row ONE scaled fp32 row, so that the fold is colsum() over an [M, C] matrix -- the launch, and
+    the summation order, of colsum(x) itself (the training step's compact last block: scale 1 reproduces its unscaled sums bitwise)."""
     assert x.dtype == torch.float32 and x.stride(-1) == 1
     M, C = x.shape
     if skip_group:                                       # x: skip_group + 1 rows per sample, the first one (class token) skipped
@@ -1116,8 +1140,14 @@ def cast_bf16_colsum(x, out=None, fold=True, skip_group=0):
         M = M // (skip_group + 1) * skip_group
     if out is None:
         out = torch.empty(M, C, dtype=torch.bfloat16, device=x.device)
-    blocks = max(1, min(1024, M // 16))
+    blocks = max(1, min(1024, M // 16)) if blocks is None else int(blocks)
     part = torch.empty(blocks, C, dtype=torch.float32, device=x.device)
+    if row_scale is not None:
+        _f32(row_scale)
+        assert row_scale.numel() >= M
+        _check(lib().msclip_cast_bf16_colsum_rowscale(_p(x), x.stride(0), _p(out), out.stride(0), M, C, _p(part), blocks, skip_group,
+                                                      _p(row_scale), _stream()), "msclip_cast_bf16_colsum_rowscale")
+        return out, (colsum(part) if fold else part)
     _check(lib().msclip_cast_bf16_colsum(_p(x), x.stride(0), _p(out), out.stride(0), M, C, _p(part), blocks, skip_group, _stream()),
            "msclip_cast_bf16_colsum")
     return out, (colsum(part) if fold else part)
@@ -1215,19 +1245,25 @@ ATTENTION_BWD_MAX_L = 272                            # msclip_attention_bwd's lo
 
 
 def layernorm_bwd(x, dy, gamma, dx, M, *, row_idx=None, row_mul=1, accumulate=True, want_param_grads=True, eps=1e-12,
-                  dxb=None, sum_part=None, sum_accumulate=False, fold=True):
+                  dxb=None, sum_part=None, sum_accumulate=False, fold=True, row_scale=None):
     """-> (dgamma, dbeta) fp32 [C] (or None).  x fp32 [*, C]; dy [M, C] bf16 / fp32; dx fp32 gets (+=) the input gradient
     at the rows the forward read.  dxb (bf16 [M, C]) + sum_part (fp32 [LN_PART_BLOCKS, C]): the written dx rows also as bf16,
-    their per-block column sums into (sum_accumulate: onto) sum_part -- colsum(sum_part) = the column sums of the new dx rows."""
+    their per-block column sums into (sum_accumulate: onto) sum_part -- colsum(sum_part) = the column sums of the new dx rows.
+    row_scale (fp32 [M], with dxb; msclip_layernorm_bwd_rowscale): dxb and sum_part take row_scale[m] * the new dx row; dx does not."""
     C = x.shape[-1]
     part = torch.empty(LN_PART_BLOCKS, 2, C, dtype=torch.float32, device=x.device) if want_param_grads else None
     if dxb is not None:
         _bf16(dxb); _f32(sum_part)
         assert dxb.shape[0] >= M and sum_part.shape == (LN_PART_BLOCKS, C) and row_idx is None and row_mul == 1
-    _check(lib().msclip_layernorm_bwd(_p(x), x.stride(0), _p(row_idx), row_mul, _p(dy), dy.stride(0),
-                                      int(dy.dtype == torch.float32), _p(gamma), _p(dx), dx.stride(0), int(accumulate),
-                                      _p(part), LN_PART_BLOCKS, M, C, eps, _p(dxb), dxb.stride(0) if dxb is not None else 0,
-                                      _p(sum_part), int(sum_accumulate), _stream()), "msclip_layernorm_bwd")
+    args = (_p(x), x.stride(0), _p(row_idx), row_mul, _p(dy), dy.stride(0), int(dy.dtype == torch.float32), _p(gamma), _p(dx),
+            dx.stride(0), int(accumulate), _p(part), LN_PART_BLOCKS, M, C, eps, _p(dxb), dxb.stride(0) if dxb is not None else 0,
+            _p(sum_part), int(sum_accumulate))
+    if row_scale is not None:
+        _f32(row_scale)
+        assert dxb is not None and row_scale.numel() >= M
+        _check(lib().msclip_layernorm_bwd_rowscale(*args, _p(row_scale), _stream()), "msclip_layernorm_bwd_rowscale")
+    else:
+        _check(lib().msclip_layernorm_bwd(*args, _stream()), "msclip_layernorm_bwd")
     if not want_param_grads:
         return None, None
     if not fold:                                         # the caller folds (FoldPlan): the partials [LN_PART_BLOCKS, 2 C] = (dgamma | dbeta)

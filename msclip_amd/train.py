@@ -35,6 +35,7 @@ from .train_conv import ConvSideBackward, ConvSideBatchNorm
 
 BF = torch.bfloat16
 F32 = torch.float32
+DROP_PATH_MODES = ("sample", "position")
 _LEAVES = ("attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
            "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
 
@@ -43,7 +44,8 @@ class TrainStep:
     """forward + backward (+ AdamW step) for one local batch.  `engine` is the model's msclip_amd.engine.Engine."""
 
     def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=1e-8, bn="frozen",
-                 without_wd=("bn", "bias", "ln"), clip_grad_norm=None, ema_decay=None):
+                 without_wd=("bn", "bias", "ln"), clip_grad_norm=None, ema_decay=None, drop_path=None, drop_path_mode="sample",
+                 drop_path_seed=0):
         """bn = "frozen": BatchNorm with its running statistics (gamma / beta trained; the inference kernels' folded
         form); bn = "batch": train-mode BatchNorm -- per-GPU batch statistics in the forward, their backward, running
         statistics updated with momentum 0.1 (what the reference's modules do in train()).
@@ -56,8 +58,25 @@ class TrainStep:
         `ema_decay`: TRAIN.EMA_DECAY in [0, 1): fp32 shadow weights (self.ema_shadow, one per entry of named_parameters(),
         buffers not included) that start as copies of the parameters and follow them on the device after every step(),
         shadow = decay * shadow + (1 - decay) * parameter; ema_assign() / ema_resume() / ema_weights() put them into the model
-        for evaluation and saving.  None, 0 and 0.0 mean no EMA (the reference's default, lib/config/default.py:146)."""
+        for evaluation and saving.  None, 0 and 0.0 mean no EMA (the reference's default, lib/config/default.py:146).
+        `drop_path`: MODEL.SPEC.VISION.DROP_PATH in [0, 1), stochastic depth on both residual branches of every vision block
+        (timm's DropPath, M.py:801, 1027-1028; the text blocks have none); None takes model.drop_path (what get_clip_model read
+        from the config), 0 / 0.0 switch it off whatever the model says.  `drop_path_mode`: "sample" = one Bernoulli(1 - p) draw
+        per image per branch (what stochastic depth means); "position" = one draw per token position per branch, shared by all
+        images -- what the reference module computes, because its blocks run sequence-first and timm draws per index of
+        dimension 0.  The masks come from a device torch.Generator seeded with `drop_path_seed` (no host
+        synchronisation; its state travels in the checkpoint); forward() leaves them in self.last_drop_masks and replays given
+        ones (drop_masks=...).  Off, the step issues exactly the launches it issued before the option existed."""
         assert bn in ("frozen", "batch")
+        if drop_path is None:
+            drop_path = getattr(model, "drop_path", 0.0)
+        if not 0.0 <= float(drop_path or 0.0) < 1.0:
+            raise ValueError(f"drop_path = {drop_path!r}: a drop rate in [0, 1) (or None for the model's, 0 for none)")
+        if drop_path_mode not in DROP_PATH_MODES:
+            raise ValueError(f"drop_path_mode = {drop_path_mode!r}: one of {DROP_PATH_MODES}")
+        self.drop_path = float(drop_path or 0.0)
+        self.drop_path_mode, self.drop_path_seed = drop_path_mode, int(drop_path_seed)
+        self.last_drop_masks = None
         if clip_grad_norm is not None and not float(clip_grad_norm) >= 0.0:
             raise ValueError(f"clip_grad_norm = {clip_grad_norm!r}: a max_norm >= 0 (or None / 0 for no clipping)")
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
@@ -86,17 +105,44 @@ class TrainStep:
         self.ema_shadow = self._ema.views if self._ema else None      # {name: fp32 view of the arena}, named_parameters() order
         self.ema_updates = 0
         self._ema_assigned = False
+        self._dp_gen = None
+        if self.drop_path:
+            self._dp_gen = torch.Generator(device=self.dev)
+            self._dp_gen.manual_seed(self.drop_path_seed)
+
+    # ------------------------------------------------------------------ stochastic depth: masks
+    def drop_mask_shape(self, Bi):
+        """Shape of one set of keep masks for a batch of Bi images: [vision blocks that run, 2 (attention, MLP branch), Bi]
+        in "sample" mode, [.., 2, tokens per image] in "position" mode."""
+        e = self.eng
+        return (sum(b is not None for b in e.vblk), 2, Bi if self.drop_path_mode == "sample" else e.Lv)
+
+    def draw_drop_masks(self, Bi):
+        """One set of keep masks (bool, on the device) from this TrainStep's generator: True with probability 1 - drop_path,
+        every entry independent.  Queued on the current stream; nothing visits the host."""
+        if self._dp_gen is None:
+            raise RuntimeError("TrainStep.draw_drop_masks() needs drop_path > 0")
+        return torch.rand(self.drop_mask_shape(Bi), generator=self._dp_gen, device=self.dev) < (1.0 - self.drop_path)
+
+    def _check_drop_masks(self, masks, Bi):
+        if masks.dtype != torch.bool or tuple(masks.shape) != self.drop_mask_shape(Bi):
+            raise ValueError(f"drop_masks: a bool tensor of shape {self.drop_mask_shape(Bi)} in {self.drop_path_mode!r} mode, got "
+                             f"{masks.dtype} {tuple(masks.shape)}")
+        return masks.to(self.dev)
 
     # ------------------------------------------------------------------ forward that keeps what the backward needs
     @hip.off_default_stream
-    def forward(self, img, tok):
+    def forward(self, img, tok, drop_masks=None):
+        """drop_masks: replay these keep masks (drop_mask_shape(batch), bool) instead of drawing a set -- also with
+        drop_path 0, where kept rows then carry the scale 1.0 exactly.  The masks used are left in self.last_drop_masks
+        (None when the step runs without stochastic depth)."""
         self._ema_live("forward")
         try:
-            return self._forward(img, tok)
+            return self._forward(img, tok, drop_masks=drop_masks)
         finally:
             self.eng.force_unfused = False
 
-    def _forward(self, img, tok, head=True, update_stats=True):
+    def _forward(self, img, tok, head=True, update_stats=True, drop_masks=None):
         """head=False (accumulate()): stop in front of the contrastive head and return the two gather payloads; the saved
         activations then wait for a backward(_dfeat=...).  update_stats=False: train-mode BatchNorm normalises with the
         batch statistics but leaves the module's running statistics alone (accumulate()'s feature pass)."""
@@ -105,6 +151,11 @@ class TrainStep:
         with torch.cuda.device(e.dev), torch.no_grad():
             Bi, Bt = img.shape[0], tok.shape[0]
             assert Bi == Bt, "a training step needs image-text pairs"
+            if drop_masks is not None:
+                drop_masks = self._check_drop_masks(drop_masks, Bi)
+            elif self.drop_path:
+                drop_masks = self.draw_drop_masks(Bi)
+            self.last_drop_masks = drop_masks
             if e.Lv > hip.ATTENTION_BWD_MAX_L or e.Lt > hip.ATTENTION_BWD_MAX_L:
                 raise NotImplementedError(f"msclip_attention_bwd covers sequences up to {hip.ATTENTION_BWD_MAX_L} tokens")
             prev = getattr(self, "saved", None)
@@ -174,6 +225,11 @@ class TrainStep:
                         conv_events.append(ev)
             M = sv["M"] = w["M"]
             sv.update(Lmax=w["Lmax"], pad=w["pad"], Mt_live=w["Mt_live"])
+            # stochastic depth: the row-scale tables of every vision block's two branches, [blocks, 2, M] fp32 (image rows 0 or
+            # 1 / keep, text rows 1); the out_proj / c_proj launches of the vision rows carry their slice, the backward reads
+            # the slices saved with the layer (None: the option is off and nothing below changes)
+            dp_tab = None if drop_masks is None else drop_path_table(drop_masks, Bi, e.Lv, M, self.drop_path_mode, 1.0 - self.drop_path)
+            dp_next = 0
             e._text_front(sv["tok"], w, Bt)
             # ---- blocks.  Xc = the residual matrix the next layer reads: the workspace's X at first; every layer that runs over
             # all rows writes its two residual updates into fresh matrices (the backward needs the layer's input and its
@@ -182,7 +238,14 @@ class TrainStep:
             for i in range(e.n_layers):
                 vb = e.vblk[i]
                 tb = e.tblk[i]
-                L = dict(adapter=None)
+                L = dict(adapter=None, rs=None)
+                if vb is not None and dp_tab is not None:
+                    L["rs"] = (dp_tab[dp_next, 0], dp_tab[dp_next, 1])          # (attention branch, MLP branch), each fp32 [M]
+                    dp_next += 1
+                rs_a, rs_m = L["rs"] if L["rs"] is not None else (None, None)
+
+                def rs_rows(t, r0, r1):                    # a launch over rows [r0, r1): its slice of the table (text-only launches: none)
+                    return t[r0:r1] if (t is not None and r0 < Mv) else None
                 if vb is not None and i in e.lateral:
                     j = e.lateral.index(i)
                     a = e.adapters[j]
@@ -238,8 +301,14 @@ class TrainStep:
                     hip.gather_rows(ao, ao_c, nc, row_idx=crow)
                     cgroups = [(0, nc, vb["w"])] if vb["w"] is tb["w"] else [(0, Bi, vb["w"]), (Bi, nc, tb["w"])]
                     xm_c = torch.empty(nc, D, dtype=F32, device=e.dev)
+                    # the compact rows' scales: the table gathered with the same row list as the activations ([2, nc]; a few KB)
+                    rs_c = None if rs_a is None else torch.stack([rs_a, rs_m]).index_select(1, crow.long()).contiguous()
+
+                    def rsc_rows(k, r0, r1):
+                        return rs_c[k, r0:r1] if (rs_c is not None and r0 < Bi) else None
                     for r0, r1, bw in cgroups:
-                        hip.gemm(ao_c[r0:r1], bw.wo, xm_c[r0:r1], bias=bw.bo, resid=xin_c[r0:r1], resid_kind=hip.RESID_F32)
+                        hip.gemm(ao_c[r0:r1], bw.wo, xm_c[r0:r1], bias=bw.bo, resid=xin_c[r0:r1], resid_kind=hip.RESID_F32,
+                                 row_scale=rsc_rows(0, r0, r1))
                     lno2_c = torch.empty(nc, D, dtype=BF, device=e.dev)
                     hip.layernorm_split(xm_c, vb["ln2"].g, vb["ln2"].b, tb["ln2"].g, tb["ln2"].b, Bi, lno2_c, nc)
                     h_c, hid_c = torch.empty(nc, 4 * D, dtype=BF, device=e.dev), torch.empty(nc, 4 * D, dtype=BF, device=e.dev)
@@ -247,14 +316,17 @@ class TrainStep:
                     for r0, r1, bw in cgroups:
                         hip.gemm(lno2_c[r0:r1], bw.wfc, h_c[r0:r1], bias=bw.bfc)
                         hip.quickgelu(h_c[r0:r1], hid_c[r0:r1])
-                        hip.gemm(hid_c[r0:r1], bw.wpr, xn_c[r0:r1], bias=bw.bpr, resid=xm_c[r0:r1], resid_kind=hip.RESID_F32)
+                        hip.gemm(hid_c[r0:r1], bw.wpr, xn_c[r0:r1], bias=bw.bpr, resid=xm_c[r0:r1], resid_kind=hip.RESID_F32,
+                                 row_scale=rsc_rows(1, r0, r1))
                     L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao,
-                             compact=dict(crow=crow, cgroups=cgroups, ao=ao_c, x_mid=xm_c, lno2=lno2_c, h=h_c, hid=hid_c, x_out=xn_c))
+                             compact=dict(crow=crow, cgroups=cgroups, ao=ao_c, x_mid=xm_c, lno2=lno2_c, h=h_c, hid=hid_c, x_out=xn_c,
+                                          rs=rs_c))
                     sv["layers"][i] = L
                     sv["compact"] = xn_c
                     continue
                 for r0, r1, bw in groups:
-                    hip.gemm(ao[r0:r1], bw.wo, XM[r0:r1], bias=bw.bo, resid=Xc[r0:r1], resid_kind=hip.RESID_F32)
+                    hip.gemm(ao[r0:r1], bw.wo, XM[r0:r1], bias=bw.bo, resid=Xc[r0:r1], resid_kind=hip.RESID_F32,
+                             row_scale=rs_rows(rs_a, r0, r1))
                 L["x_mid"] = XM if fresh else XM[r_lo:M].clone()
                 XN = torch.empty(M, D, dtype=F32, device=e.dev) if fresh else Xc
                 lno2 = torch.empty(M, D, dtype=BF, device=e.dev)
@@ -274,7 +346,8 @@ class TrainStep:
                         hip.gemm(lno2[r0:r1], bw.wfc, h[r0:r1], bias=bw.bfc)
                         hip.quickgelu(h[r0:r1], hid[r0:r1])
                 for r0, r1, bw in groups:
-                    hip.gemm(hid[r0:r1], bw.wpr, XN[r0:r1], bias=bw.bpr, resid=XM[r0:r1], resid_kind=hip.RESID_F32)
+                    hip.gemm(hid[r0:r1], bw.wpr, XN[r0:r1], bias=bw.bpr, resid=XM[r0:r1], resid_kind=hip.RESID_F32,
+                             row_scale=rs_rows(rs_m, r0, r1))
                 L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao, lno2=lno2, h=h, hid=hid)
                 sv["layers"][i] = L
                 Xc = XN
@@ -467,10 +540,13 @@ class TrainStep:
                 head(sv["fv_raw"], dfi, sv["hv"], e.w_vproj, e.ln_post, "visual.proj", "visual.ln_post", row_mul=e.Lv)
                 head(sv["ft_raw"], dft, sv["ht"], e.w_tproj, e.ln_final, "text_projection", "ln_final", row_idx=sv["eot"])
 
-            def cast_with_bias_sums(dX, dY, r_lo, groups):
+            def cast_with_bias_sums(dX, dY, r_lo, groups, rs=None):
                 """dY[r_lo:M] = bf16(dX[r_lo:M]) -- the operand of a projection's dgrad / wgrad GEMMs -- and {id(block
                 weights): column sums of the group's rows} = that projection's bias gradient; one pass over dX when a
-                single (shared) weight set covers all rows."""
+                single (shared) weight set covers all rows.  rs (fp32 [M], stochastic depth): copy and sums of rs[row] * dX[row]
+                -- what everything upstream of the projection's scaled residual add sees -- from the same one pass per group."""
+                if rs is not None:
+                    return {id(bw): hip.cast_bf16_colsum(dX[r0:r1], dY[r0:r1], fold=False, row_scale=rs[r0:r1])[1] for r0, r1, bw in groups}
                 if len(groups) == 1 and groups[0][0] == r_lo and groups[0][1] == M:
                     _, s = hip.cast_bf16_colsum(dX[r_lo:M], dY[r_lo:M], fold=False)    # partial sums: folded with the others (set_bias)
                     return {id(groups[0][2]): s}
@@ -523,11 +599,12 @@ class TrainStep:
                     return wts[id(bw)][which]
                 return (bw.wpr, bw.wfc, bw.wo, bw.wqkv)[which].t().contiguous()
 
-            def ln_bwd_segments(x_saved, dlno, segs, groups, r_lo, which, i, dY_next):
+            def ln_bwd_segments(x_saved, dlno, segs, groups, r_lo, which, i, dY_next, rs=None):
                 """LayerNorm backward (`which` = "ln1" / "ln2" of block i) of every row segment: dX += its input gradient.  With
                 dY_next (bf16 [M, D]) the same pass leaves bf16(new dX) there -- the output gradient of the projection in front of
                 this LayerNorm point, operand of its dgrad / wgrad GEMMs -- and returns {id(block weights): that projection's bias
-                gradient} from per-block column sums (no cast_bf16_colsum pass over dX); else returns None."""
+                gradient} from per-block column sums (no cast_bf16_colsum pass over dX); else returns None.  rs (fp32 [M], with
+                dY_next): that projection sits behind a DropPath -- the copy and the sums of the image rows carry rs[row], dX does not."""
                 parts = {}
                 for r0, r1, b in segs:
                     kw = {}
@@ -536,7 +613,8 @@ class TrainStep:
                         first = gid not in parts
                         if first:
                             parts[gid] = torch.empty(hip.LN_PART_BLOCKS, D, dtype=F32, device=dev)
-                        kw = dict(dxb=dY_next[r0:r1], sum_part=parts[gid], sum_accumulate=not first)
+                        kw = dict(dxb=dY_next[r0:r1], sum_part=parts[gid], sum_accumulate=not first,
+                                  row_scale=rs[r0:r1] if (rs is not None and r0 < Mv) else None)
                     pre = f"visual.transformer.resblocks.{i}" if b is e.vblk[i] else f"transformer.resblocks.{i}"
                     part, _ = hip.layernorm_bwd(x_saved[r0 - r_lo:r1 - r_lo], dlno[r0:r1], b[which].g, dX[r0:r1], r1 - r0, fold=False, **kw)
                     ln_param_grads(part, f"{pre}.{'ln_1' if which == 'ln1' else 'ln_2'}")
@@ -559,11 +637,22 @@ class TrainStep:
                     nc = Bi + Bt
                     xm_c, lno2_c, h_c, hid_c, ao_c = cm["x_mid"], cm["lno2"], cm["h"], cm["hid"], cm["ao"]
                     dlno2_c = torch.empty(nc, D, dtype=F32, device=dev)
-                    dy_c = hip.cast_bf16(dXC)
+                    rs_c = cm["rs"]                                  # [2, nc] row scales of the live rows (stochastic depth), or None
+
+                    def cast_c(k):
+                        """bf16(dXC) and, per weight group, its column sums -- of rs_c[k][row] * dXC[row] behind a DropPath: one
+                        library pass per group writes the scaled copy and the scaled fp32 rows (a partial row per row), which
+                        the unscaled path's own colsum launch then folds (same shape, same order: scale 1 gives its bits)."""
+                        if rs_c is None:
+                            return hip.cast_bf16(dXC), {id(bw): hip.colsum(dXC[r0:r1]) for r0, r1, bw in cm["cgroups"]}
+                        y = torch.empty(nc, D, dtype=BF, device=dev)
+                        return y, {id(bw): hip.cast_bf16_colsum(dXC[r0:r1], y[r0:r1], row_scale=rs_c[k, r0:r1], blocks=r1 - r0)[1]
+                                   for r0, r1, bw in cm["cgroups"]}
+                    dy_c, bsum_c = cast_c(1)
                     for r0, r1, bw in cm["cgroups"]:
                         p = names[id(bw)]
                         grads[p + ".mlp.c_proj.weight"] = _wgrad(dy_c[r0:r1], hid_c[r0:r1], r1 - r0)
-                        grads[p + ".mlp.c_proj.bias"] = hip.colsum(dXC[r0:r1])
+                        grads[p + ".mlp.c_proj.bias"] = bsum_c[id(bw)]
                         dh_c = torch.empty(r1 - r0, 4 * D, dtype=BF, device=dev)
                         hip.quickgelu_bwd(h_c[r0:r1], _dgrad(dy_c[r0:r1], w_t(bw, 0)), dh_c)
                         grads[p + ".mlp.c_fc.weight"] = _wgrad(dh_c, lno2_c[r0:r1], r1 - r0)
@@ -576,12 +665,12 @@ class TrainStep:
                     # dXC is now the gradient wrt the rows behind the attention (x_mid): out_proj on the compact rows, then both
                     # results go back to their rows of the token matrix -- the attention output's gradient (zero elsewhere) and,
                     # through the residual connection, the block input's
-                    dy2_c = hip.cast_bf16(dXC)
+                    dy2_c, bsum_c = cast_c(0)
                     dao_c = torch.empty(nc, D, dtype=BF, device=dev)
                     for r0, r1, bw in cm["cgroups"]:
                         p = names[id(bw)]
                         grads[p + ".attn.out_proj.weight"] = _wgrad(dy2_c[r0:r1], ao_c[r0:r1], r1 - r0)
-                        grads[p + ".attn.out_proj.bias"] = hip.colsum(dXC[r0:r1])
+                        grads[p + ".attn.out_proj.bias"] = bsum_c[id(bw)]
                         _dgrad(dy2_c[r0:r1], w_t(bw, 2), dao_c[r0:r1])
                     rows_c = cm["crow"].long()
                     dao = torch.zeros(M, D, dtype=BF, device=dev)
@@ -596,7 +685,7 @@ class TrainStep:
                         carry = None
                     else:
                         dY = torch.empty(M, D, dtype=BF, device=dev)
-                        bsum = cast_with_bias_sums(dX, dY, r_lo, groups)
+                        bsum = cast_with_bias_sums(dX, dY, r_lo, groups, rs=L["rs"][1] if L["rs"] is not None else None)
                     # gradients of the LayerNorm outputs stay fp32: they are only read by the LayerNorm backward, whose dbeta /
                     # dgamma are column sums of nearly cancelling terms (a bf16 dy costs 10-30 % on those sums at small batch)
                     dlno = torch.empty(M, D, dtype=F32, device=dev)
@@ -628,9 +717,10 @@ class TrainStep:
                     del dh
                     # attention half.  dX behind the ln_2 backward is out_proj's output gradient: its bf16 copy and bias sums leave with that pass
                     dY2 = torch.empty(M, D, dtype=BF, device=dev)          # not dY again: the lane stream may still read it (c_proj wgrad)
-                    bsum = ln_bwd_segments(L["x_mid"], dlno, segs, groups, r_lo, "ln2", i, dY2 if fuse_cast else None)
+                    rs_a = L["rs"][0] if L["rs"] is not None else None
+                    bsum = ln_bwd_segments(L["x_mid"], dlno, segs, groups, r_lo, "ln2", i, dY2 if fuse_cast else None, rs=rs_a)
                     if bsum is None:
-                        bsum = cast_with_bias_sums(dX, dY2, r_lo, groups)
+                        bsum = cast_with_bias_sums(dX, dY2, r_lo, groups, rs=rs_a)
                     dao = torch.empty(M, D, dtype=BF, device=dev)
                     dqkv = torch.empty(M, 3 * D, dtype=BF, device=dev)      # attention_bwd writes every row of the towers that ran
                     for r0, r1, bw in groups:
@@ -677,7 +767,9 @@ class TrainStep:
                         [(a, b_) for a, b_, _ in below["segs"]] == [(a, b_) for a, b_, _ in segs] and
                         [(a, b_) for a, b_, _ in below["groups"]] == [(a, b_) for a, b_, _ in groups])
                 dY_below = torch.empty(M, D, dtype=BF, device=dev) if (fuse_cast and same) else None
-                bs = ln_bwd_segments(L["x_in"], dlno, segs, groups, r_lo, "ln1", i, dY_below)
+                # (behind a DropPath of the block below: its MLP branch's scale rides on this pass)
+                bs = ln_bwd_segments(L["x_in"], dlno, segs, groups, r_lo, "ln1", i, dY_below,
+                                     rs=below["rs"][1] if (dY_below is not None and below["rs"] is not None) else None)
                 if bs is not None:
                     # keyed by THIS block's weight sets; the block below holds its own: same row ranges, so map by range
                     by_range = {(g0, g1): bs[id(bw)] for g0, g1, bw in groups}
@@ -750,7 +842,7 @@ class TrainStep:
 
     # ------------------------------------------------------------------ exact large-batch step over chunks
     @hip.off_default_stream
-    def accumulate(self, chunks, clone=False, check_features=False):
+    def accumulate(self, chunks, clone=False, check_features=False, drop_masks=None):
         """-> (loss, grads) of ONE contrastive batch made of all the chunks' pairs, computed one chunk at a time; follow it
         with step(grads).  chunks: a sequence indexed twice, K >= 1 pairs (img, tok), each acceptable to forward() (a staged
         engine.Captions included); chunk sizes may differ, N = sum of them.
@@ -776,7 +868,12 @@ class TrainStep:
 
         LIFETIME: the returned tensors are views of persistent fp32 accumulators owned by this TrainStep (stable addresses:
         the optimizer table is not rebuilt); they are valid until the next accumulate().  clone=True returns owned copies.
-        K = 1 reproduces forward() + backward() bitwise (token_embedding.weight: atomic scatter-add, to rounding)."""
+        K = 1 reproduces forward() + backward() bitwise (token_embedding.weight: atomic scatter-add, to rounding).
+
+        Stochastic depth: ONE set of keep masks per chunk, drawn before the feature pass (chunk order) and used by both of the
+        chunk's forwards -- the banked features and the differentiated ones belong to the same network.  drop_masks: a
+        sequence of K mask tensors to replay instead (forward()'s drop_masks, per chunk); the sets used are left in
+        self.last_drop_masks as a list."""
         if C.comm.collectives or C.comm.world_size > 1:
             raise NotImplementedError("TrainStep.accumulate() covers a single process: chunks composed with ranks (world size "
                                       f"{C.comm.world_size}) are not implemented")
@@ -784,8 +881,10 @@ class TrainStep:
         K = len(chunks)
         if K < 1:
             raise ValueError("TrainStep.accumulate() needs at least one (img, tok) chunk")
+        if drop_masks is not None and len(drop_masks) != K:
+            raise ValueError(f"TrainStep.accumulate(): {len(drop_masks)} drop_masks for {K} chunks")
         try:
-            return self._accumulate(chunks, K, clone, check_features)
+            return self._accumulate(chunks, K, clone, check_features, drop_masks)
         finally:
             self.eng.force_unfused = False
 
@@ -795,9 +894,11 @@ class TrainStep:
             sv["w"].pop("held", None)
             self.saved = None
 
-    def _feature_pass(self, chunks):
-        """Pass 1 of accumulate(): -> (bank_i, bank_t bf16 [N, 2E], [first row of every chunk] + [N])."""
+    def _feature_pass(self, chunks, masks=None):
+        """Pass 1 of accumulate(): -> (bank_i, bank_t bf16 [N, 2E], [first row of every chunk] + [N]).  masks[k]: chunk k's
+        stochastic-depth keep masks (None: off)."""
         e = self.eng
+        masks = masks if masks is not None else [None] * len(chunks)
         sizes = [int(chunks[k][0].shape[0]) for k in range(len(chunks))]
         starts = [0]
         for b in sizes:
@@ -807,7 +908,7 @@ class TrainStep:
         bank_t = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
         for k in range(len(chunks)):
             img, tok = chunks[k]
-            pi, pt = self._forward(img, tok, head=False, update_stats=False)
+            pi, pt = self._forward(img, tok, head=False, update_stats=False, drop_masks=masks[k])
             self._release_saved()                                                # nothing is kept for a backward
             bank_i[starts[k]:starts[k + 1]] = pi
             bank_t[starts[k]:starts[k + 1]] = pt
@@ -861,10 +962,17 @@ class TrainStep:
             ev.record(torch.cuda.current_stream(self.eng.dev))
             ev_list.append((name, ev))
 
-    def _accumulate(self, chunks, K, clone, check_features):
+    def _accumulate(self, chunks, K, clone, check_features, drop_masks=None):
         e = self.eng
         self._mark("start")
-        bank_i, bank_t, starts = self._feature_pass(chunks)
+        if drop_masks is not None:
+            masks = [self._check_drop_masks(drop_masks[k], int(chunks[k][0].shape[0])) for k in range(K)]
+        elif self.drop_path:
+            e.refresh()
+            masks = [self.draw_drop_masks(int(chunks[k][0].shape[0])) for k in range(K)]
+        else:
+            masks = [None] * K
+        bank_i, bank_t, starts = self._feature_pass(chunks, masks)
         self._mark("features")
         loss, dfeat = self._bank_head(bank_i, bank_t, starts)
         self._mark("head")
@@ -872,7 +980,7 @@ class TrainStep:
             bank_i = bank_t = None
         for k in range(K):
             img, tok = chunks[k]
-            pi, pt = self._forward(img, tok, head=False)
+            pi, pt = self._forward(img, tok, head=False, drop_masks=masks[k])
             if check_features:
                 r0, r1 = starts[k], starts[k + 1]
                 for name, now, banked in (("image", pi, bank_i[r0:r1]), ("text", pt, bank_t[r0:r1])):
@@ -892,6 +1000,7 @@ class TrainStep:
                 acc.add(g, 0 if k == 0 else 1)
                 self._mark("accumulate")
             del g
+        self.last_drop_masks = masks if masks[0] is not None else None
         out = acc.views
         return loss, ({key: t.clone() for key, t in out.items()} if clone else dict(out))
 
@@ -1220,7 +1329,8 @@ def _optimizer_state_dict(ts):
 def save_checkpoint(model, ts, path, step, model_name="", perf=0.0):
     """The reference's resumable checkpoint dict (lib/utils/utils.py:157-200): 'step', 'model', 'state_dict', 'perf',
     'optimizer', and with TrainStep(ema_decay=...) 'ema_shadow_states' = {parameter name: CPU tensor}, the reference's
-    `ema_model.shadow` (utils.py:187-188); without EMA the file is what it was before the key existed.  'state_dict' holds the
+    `ema_model.shadow` (utils.py:187-188); without EMA the file is what it was before the key existed.  With drop_path > 0 also
+    'drop_path_rng_state', the state of the TrainStep's mask generator (absent otherwise).  'state_dict' holds the
     live weights: not to be called between ema_assign() and ema_resume().  Rank 0 only under N > 1."""
     ts._ema_live("save_checkpoint")
     if not C.comm.is_main_process():
@@ -1230,13 +1340,16 @@ def save_checkpoint(model, ts, path, step, model_name="", perf=0.0):
            "optimizer": _optimizer_state_dict(ts)}
     if ts.ema_shadow is not None:
         out["ema_shadow_states"] = {k: v.detach().cpu() for k, v in ts.ema_shadow.items()}
+    if ts._dp_gen is not None:                        # stochastic depth: the mask generator continues where it stopped
+        out["drop_path_rng_state"] = ts._dp_gen.get_state()
     torch.save(out, path)
 
 
 def resume_checkpoint(model, ts, path):
     """-> the step to continue from.  Loads the module (strict, aliases checked), the AdamW moments and the step count.
     With TrainStep(ema_decay=...) also the shadow weights from 'ema_shadow_states'; a checkpoint without that key is refused,
-    as the reference asserts (lib/utils/utils.py:129-133).  Without EMA the key is ignored."""
+    as the reference asserts (lib/utils/utils.py:129-133).  Without EMA the key is ignored.  With drop_path > 0 the mask
+    generator takes 'drop_path_rng_state'; where the key is absent (an older checkpoint) it is reseeded from drop_path_seed."""
     from .checkpoint import check_aliases, extract_state_dict
     ts._ema_live("resume_checkpoint")
     obj = torch.load(path, map_location="cpu", weights_only=False)
@@ -1256,20 +1369,28 @@ def resume_checkpoint(model, ts, path):
     ts.steps = int(opt["msclip"]["steps"])
     if ts.ema_shadow is not None:
         ts._ema.load(obj["ema_shadow_states"])
+    if ts._dp_gen is not None:
+        # a checkpoint written before the key existed (or without stochastic depth): the masks restart from the seed
+        if "drop_path_rng_state" in obj:
+            ts._dp_gen.set_state(obj["drop_path_rng_state"])
+        else:
+            ts._dp_gen.manual_seed(ts.drop_path_seed)
     ts._plan = None                                   # the cached optimizer table points at the moments just replaced
     ts.eng.refresh(force=True)
     return int(obj.get("step", ts.steps))
 
 
-def from_config(model, config, bn="batch"):
+def from_config(model, config, bn="batch", drop_path_mode="sample"):
     """TrainStep with the reference yaml's optimizer block (experiments/model/b32.yaml:32-52 + the msclips overlays):
     TRAIN.OPTIMIZER (only adamW is implemented: anything else raises), TRAIN.LR / WD / WITHOUT_WD_LIST, TRAIN.OPTIMIZER_ARGS
     (betas / eps; absent => torch.optim.AdamW's defaults, what `AdamW(params, lr=..., weight_decay=..., **{})` gives),
     CUSTOM.LR_SHARE / WD_SHARE for the modality-shared tensors (already scaled with the world size by update_config,
     lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off), TRAIN.EMA_DECAY
-    (shadow weights updated inside step(); absent or 0.0 = off).
+    (shadow weights updated inside step(); absent or 0.0 = off), MODEL.SPEC.VISION.DROP_PATH (stochastic depth on the vision
+    blocks, one draw per image per branch unless drop_path_mode says "position"; absent or 0.0 = off).
     bn = "batch" (default): train-mode BatchNorm as the reference's modules run in train(); "frozen": running statistics."""
-    ts = TrainStep(model, bn=bn, ema_decay=ema_setting(config), **optimizer_settings(config))
+    ts = TrainStep(model, bn=bn, ema_decay=ema_setting(config), drop_path=drop_path_setting(config), drop_path_mode=drop_path_mode,
+                   **optimizer_settings(config))
     ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
     ts.schedule = lr_schedule(config)            # TRAIN.LR_SCHEDULER of the yaml (None when the config has none)
     return ts
@@ -1325,6 +1446,39 @@ def ema_setting(config):
     """TRAIN.EMA_DECAY of a reference config as TrainStep's `ema_decay` (needs no GPU): None when the key is absent or 0.0,
     the reference's default (lib/config/default.py:146; its run name carries 'ema<decay>' only when > 0, :268-270)."""
     return float(config.TRAIN.get("EMA_DECAY", 0.0) or 0.0) or None
+
+
+def drop_path_setting(config):
+    """MODEL.SPEC.VISION.DROP_PATH of a reference config (M.py:3188) as TrainStep's `drop_path` (needs no GPU): 0.0 when the key
+    is absent -- an explicit "off", so that the config and not a stale model attribute decides; a rate outside [0, 1) raises."""
+    p = float(config.MODEL.SPEC.VISION.get("DROP_PATH", 0.0) or 0.0)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"MODEL.SPEC.VISION.DROP_PATH = {p!r}: a drop rate in [0, 1)")
+    return p
+
+
+def drop_path_table(keep_draws, Bi, Lv, M, mode, keep):
+    """The fp32 row-scale tables of the launches that carry stochastic depth, from one set of Bernoulli draws (pure tensor code:
+    runs wherever keep_draws lives, CPU included).
+    keep_draws: bool [vision blocks, 2 (attention branch, MLP branch), Bi] in mode "sample" -- one draw per image -- or
+    [vision blocks, 2, Lv] in mode "position" -- one draw per token position, shared by all images (timm's DropPath on the
+    reference's sequence-first blocks).  -> fp32 [vision blocks, 2, M]: row b * Lv + l of the token matrix (image b, token l)
+    holds 1 / keep where its draw kept the branch and 0 where it dropped it; rows Bi * Lv .. M -- the text tokens, sized to the
+    launch's upper bound M so that a packed caption batch needs nothing more -- hold 1."""
+    if mode not in DROP_PATH_MODES:
+        raise ValueError(f"mode = {mode!r}: one of {DROP_PATH_MODES}")
+    n = Bi if mode == "sample" else Lv
+    if keep_draws.dtype != torch.bool or keep_draws.dim() != 3 or keep_draws.shape[1] != 2 or keep_draws.shape[2] != n:
+        raise ValueError(f"keep_draws: bool [blocks, 2, {n}] in mode {mode!r}, got {keep_draws.dtype} {tuple(keep_draws.shape)}")
+    if not 0.0 < keep <= 1.0 or M < Bi * Lv:
+        raise ValueError(f"keep = {keep!r} (0 < keep <= 1), M = {M} (>= {Bi * Lv} image rows)")
+    nb = keep_draws.shape[0]
+    per = keep_draws[:, :, :, None].expand(nb, 2, Bi, Lv) if mode == "sample" else keep_draws[:, :, None, :].expand(nb, 2, Bi, Lv)
+    out = torch.ones(nb, 2, M, dtype=F32, device=keep_draws.device)
+    img = out[:, :, :Bi * Lv].view(nb, 2, Bi, Lv)
+    img.copy_(torch.where(per, torch.tensor(1.0 / keep, dtype=F32, device=keep_draws.device),
+                          torch.zeros((), dtype=F32, device=keep_draws.device)))
+    return out
 
 
 def optimizer_settings(config):

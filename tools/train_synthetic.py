@@ -1,7 +1,7 @@
 """A few optimizer steps of the MS-CLIP-S training step on synthetic image / caption pairs (random-init weights):
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
-                                    [--accumulate K] [--clip-grad-norm X] [--ema-decay D]
+                                    [--accumulate K] [--clip-grad-norm X] [--ema-decay D] [--drop-path P [--drop-path-mode M]]
 
 --accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
 TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
@@ -11,6 +11,10 @@ every fifth step also prints the norm before clipping.
 
 --ema-decay D: TRAIN.EMA_DECAY, shadow weights follow the parameters inside step() (on the device); at the end the
 inference-path loss is also printed under the shadow weights (TrainStep.ema_weights()), next to the live one.
+
+--drop-path P: MODEL.SPEC.VISION.DROP_PATH, stochastic depth on both residual branches of every vision block (masks drawn on
+the device, one draw per image -- or with --drop-path-mode position per token position, as the reference module does).  The
+training losses then carry the masks' noise; the inference-path loss at the end does not.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -43,6 +47,10 @@ def main():
                     help="X > 0: clip the gradients to the global L2 norm X inside step() (TRAIN.CLIP_GRAD_NORM; 0 = off)")
     ap.add_argument("--ema-decay", type=float, default=0.0,
                     help="D in (0, 1): keep an exponential moving average of the weights inside step() (TRAIN.EMA_DECAY; 0 = off)")
+    ap.add_argument("--drop-path", type=float, default=0.0,
+                    help="P in (0, 1): stochastic depth on the vision blocks' residual branches (MODEL.SPEC.VISION.DROP_PATH; 0 = off)")
+    ap.add_argument("--drop-path-mode", choices=("sample", "position"), default="sample",
+                    help="one draw per image (sample) or per token position, shared by the batch (position: the reference module's layout)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -56,12 +64,13 @@ def main():
     if dist.is_initialized():                              # a process group exists: leave the legacy default stream (once, explicitly)
         from msclip_amd import hip
         hip.use_compute_stream(dev)
-    cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm), "TRAIN.EMA_DECAY", str(args.ema_decay)])
+    cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm), "TRAIN.EMA_DECAY", str(args.ema_decay),
+                                    "MODEL.SPEC.VISION.DROP_PATH", str(args.drop_path)])
     from bench import load_schema
     model = get_clip_model(cfg)
     model.load_state_dict(synth.synth_state_dict(load_schema(args.model), seed=0), strict=True)
     model = model.to(dev).eval()
-    ts = train.from_config(model, cfg, bn=args.bn)
+    ts = train.from_config(model, cfg, bn=args.bn, drop_path_mode=args.drop_path_mode)
     ts.lr = ts.lr_share = args.lr                          # (the schedule scales these base rates epoch by epoch)
     rank = C.comm.rank
     data = [(synth.synth_images(args.batch, seed=1000 * rank + 10 + i).to(dev),
