@@ -25,6 +25,9 @@ EXT_VERSION_MACRO = "MSCLIP_EXT_ABI_VERSION"
 # so it is read with those names known (load(..., known=...))
 EXT2_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext2.h")
 EXT2_VERSION_MACRO = "MSCLIP_EXT2_ABI_VERSION"
+# the third extension header (the LAMB entry points and their table item), read like the second
+EXT3_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext3.h")
+EXT3_VERSION_MACRO = "MSCLIP_EXT3_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 

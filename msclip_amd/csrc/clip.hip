@@ -8,6 +8,7 @@
 #include "multi_tensor.h"
 #include "plan.h"
 #include "../../include/msclip_hip.h"
+#include "../../include/msclip_ext3.h"
 
 namespace {
 
@@ -74,6 +75,44 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
   }
 }
 
+// LAMB's trust ratios (include/msclip_ext3.h; the partials are lamb_partials_kernel's of optim.hip, two per chunk): workgroup k
+// adds parameter k's {sum p^2, sum u^2} over its chunks as clip_coef_kernel adds -- thread t takes chunks t, t + 256, ... in
+// double, then the same tree in double.  In this file because the rule is made of comparisons that a NaN must fail and a
+// division by Inf that must give 0.
+__global__ __launch_bounds__(256) void lamb_ratios_kernel(const float* __restrict__ partials, const int* __restrict__ first_chunk,
+                                                          int n_params, long long n_chunks, int trust_clip,
+                                                          float* __restrict__ out) {
+  const int k = blockIdx.x;
+  long long c0 = first_chunk[k], c1 = first_chunk[k + 1];
+  c0 = c0 < 0 ? 0 : (c0 > n_chunks ? n_chunks : c0);         // (a table that does not match the partials reads none beyond them)
+  c1 = c1 < 0 ? 0 : (c1 > n_chunks ? n_chunks : c1);
+  double sw = 0.0, su = 0.0;
+  for (long long c = c0 + threadIdx.x; c < c1; c += 256) {
+    sw += (double)partials[2 * c];
+    su += (double)partials[2 * c + 1];
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    sw += __shfl_xor(sw, o, 64);
+    su += __shfl_xor(su, o, 64);
+  }
+  __shared__ double red[8];
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sw;
+    red[4 + (threadIdx.x >> 6)] = su;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float wn = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    const float un = (float)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+    float r = (wn > 0.f && un > 0.f) ? wn / un : 1.f;        // NaN: both comparisons false; un = Inf: 0
+    if (trust_clip && r > 1.f) r = 1.f;
+    out[k] = r;
+    out[(size_t)n_params + k] = wn;
+    out[2 * (size_t)n_params + k] = un;
+  }
+}
+
 }  // namespace
 
 extern "C" int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, float* partials, long long n_partials,
@@ -102,5 +141,16 @@ extern "C" int msclip_clip_coef(const float* partials, long long n, float max_no
   MSCLIP_PLAN_HOOK(msclip_clip_coef, stream, partials, n, max_norm, out);
   if (!partials || !out || n <= 0 || !(max_norm >= 0.f) || (((size_t)partials | (size_t)out) & 3)) return MSCLIP_EINVAL;
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out);
+  return msclip_launch_status();
+}
+
+extern "C" int msclip_lamb_ratios(const float* partials, const int* first_chunk_dev, int n_params, long long n_chunks,
+                                  int trust_clip, float* out, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_lamb_ratios, stream, partials, first_chunk_dev, n_params, n_chunks, trust_clip, out);
+  if (!partials || !first_chunk_dev || !out || n_params <= 0 || n_chunks <= 0 ||
+      (((size_t)partials | (size_t)first_chunk_dev | (size_t)out) & 3))
+    return MSCLIP_EINVAL;
+  hipLaunchKernelGGL(lamb_ratios_kernel, dim3(n_params), dim3(256), 0, (hipStream_t)stream, partials, first_chunk_dev, n_params,
+                     n_chunks, trust_clip, out);
   return msclip_launch_status();
 }

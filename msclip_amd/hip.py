@@ -33,6 +33,11 @@ EmaTensor = _EXT.structs["msclip_ema_tensor"]
 _EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
 EXT2_ABI_VERSION = _EXT2.version
 EXT2_EXPORTS = tuple(_EXT2.protos)
+# include/msclip_ext3.h: the LAMB entry points (TRAIN.OPTIMIZER lamb), a fourth table
+_EXT3 = abi.load(abi.EXT3_HEADER, abi.EXT3_VERSION_MACRO, known=tuple(_ABI.structs))
+EXT3_ABI_VERSION = _EXT3.version
+EXT3_EXPORTS = tuple(_EXT3.protos)
+LambTensor = _EXT3.structs["msclip_lamb_tensor"]
 CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
 
 
@@ -94,6 +99,15 @@ def lib():
         if L.msclip_ext2_abi_version() != EXT2_ABI_VERSION:
             raise HipUnavailable(f"{LIB_PATH} has row-scale extension ABI version {L.msclip_ext2_abi_version()}, this binding needs "
                                  f"{EXT2_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
+        for name, (restype, argtypes) in _EXT3.protos.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext3.h declares: rebuild "
+                                     "(bash msclip_amd/csrc/build.sh)")
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.msclip_ext3_abi_version() != EXT3_ABI_VERSION:
+            raise HipUnavailable(f"{LIB_PATH} has LAMB extension ABI version {L.msclip_ext3_abi_version()}, this binding needs "
+                                 f"{EXT3_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1770,10 +1784,12 @@ class AdamwPlan:
     where the previous item's end (the pieces of one parameter that differ in their packed copy): such a run is one entry
     of the norm's table, so the norm is chunked over whole gradient tensors, as hip.grad_norm chunks them."""
 
+    _item = AdamwTensor                                      # (LambPlan: the same members, then its own)
+
     def __init__(self, items, joined=None):
         n = len(items)
         self.n = n
-        self.arr = (AdamwTensor * max(n, 1))()
+        self.arr = (self._item * max(n, 1))()
         self.device = items[0][0].device if n else None
         # parameters, moments and packed copies live as long as the table; the gradients do not (set_grads re-points them)
         self.keep = [(it[0], it[2], it[3]) + tuple(it[6:7]) for it in items]
@@ -1833,6 +1849,57 @@ class AdamwPlan:
             _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
             coef = ctypes.c_void_p(self.clip.data_ptr() + 4)
             _check(L.msclip_adamw_multi_clipped(self.arr, self.n, beta1, beta2, eps, step, coef, st), "msclip_adamw_multi_clipped")
+
+
+class LambPlan(AdamwPlan):
+    """The host-side tensor table of the LAMB step (include/msclip_ext3.h): AdamwPlan's items, `joined` flags, set_grads and
+    clipping table, plus per item the parameter it belongs to -- a run of joined items is ONE parameter with one trust ratio
+    -- and whether its rate is scaled by that ratio: weight_decay != 0, or always (always_adapt); set_rates keeps the flag
+    current.  Owns `partials` (two fp32 per 32 K-element chunk of an item) and `result` ([3, n_params]: ratio, ||w||, ||u||),
+    both never zeroed -- every slot is overwritten by the chunk / workgroup that owns it -- and the device array `first_chunk`
+    (n_params + 1 ints, uploaded here once)."""
+    _item = LambTensor
+
+    def __init__(self, items, joined=None, always_adapt=False):
+        super().__init__(items, joined)
+        self.always_adapt = bool(always_adapt)
+        chunks, first = 0, []
+        for a, s in zip(self.arr, self.sq_of):
+            if s is not None:
+                first.append(chunks)
+            a.param, a.adapt = len(first) - 1, int(self.always_adapt or a.weight_decay != 0.0)
+            chunks += (a.n + CLIP_CHUNK - 1) // CLIP_CHUNK
+        self.n_params, self.n_chunks = len(first), chunks
+        assert self.n_params == self.n_sq
+        if self.n:
+            self.first_chunk = torch.tensor(first + [chunks], dtype=torch.int32, device=self.device)
+            self.lamb_partials = torch.empty(2 * chunks, dtype=torch.float32, device=self.device)
+            self.result = torch.empty(3, self.n_params, dtype=torch.float32, device=self.device)
+            self.ratio, self.param_norm, self.update_norm = self.result[0], self.result[1], self.result[2]
+
+    def set_rates(self, rates):
+        """rates: [(lr, weight_decay)] per item; an item adapts where its weight_decay is not 0 (or always_adapt)."""
+        for a, (lr, wd) in zip(self.arr, rates):
+            a.lr, a.weight_decay, a.adapt = lr, wd, int(self.always_adapt or wd != 0.0)
+
+    def run(self, beta1, beta2, eps, step, max_norm=None, trust_clip=False):
+        """[msclip_grad_sumsq -> msclip_clip_coef ->] msclip_lamb_partials -> msclip_lamb_ratios -> msclip_lamb_apply on the
+        current stream, nothing read back.  Afterwards self.ratio / param_norm / update_norm ([n_params] views of `result`)
+        hold this step's values; with max_norm, self.norm / self.coef as after AdamwPlan.run."""
+        if not self.n:
+            return
+        with torch.cuda.device(self.device):
+            L, st = lib(), _stream()
+            coef = None
+            if max_norm is not None:
+                _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
+                _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
+                coef = ctypes.c_void_p(self.clip.data_ptr() + 4)
+            _check(L.msclip_lamb_partials(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.lamb_partials),
+                                          2 * self.n_chunks, st), "msclip_lamb_partials")
+            _check(L.msclip_lamb_ratios(_p(self.lamb_partials), _p(self.first_chunk), self.n_params, self.n_chunks,
+                                        int(bool(trust_clip)), _p(self.result), st), "msclip_lamb_ratios")
+            _check(L.msclip_lamb_apply(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.result), st), "msclip_lamb_apply")
 
 
 def adamw_multi(items, beta1, beta2, eps, step):

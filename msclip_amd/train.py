@@ -40,12 +40,15 @@ _LEAVES = ("attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "
            "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
 
 
+OPTIMIZERS = {"adamw": 1e-8, "lamb": 1e-6}              # TrainStep(optimizer=...): the default eps of each
+
+
 class TrainStep:
     """forward + backward (+ AdamW step) for one local batch.  `engine` is the model's msclip_amd.engine.Engine."""
 
-    def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=1e-8, bn="frozen",
+    def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=None, bn="frozen",
                  without_wd=("bn", "bias", "ln"), clip_grad_norm=None, ema_decay=None, drop_path=None, drop_path_mode="sample",
-                 drop_path_seed=0):
+                 drop_path_seed=0, optimizer="adamw", trust_clip=False, always_adapt=False):
         """bn = "frozen": BatchNorm with its running statistics (gamma / beta trained; the inference kernels' folded
         form); bn = "batch": train-mode BatchNorm -- per-GPU batch statistics in the forward, their backward, running
         statistics updated with momentum 0.1 (what the reference's modules do in train()).
@@ -66,8 +69,19 @@ class TrainStep:
         images -- what the reference module computes, because its blocks run sequence-first and timm draws per index of
         dimension 0.  The masks come from a device torch.Generator seeded with `drop_path_seed` (no host
         synchronisation; its state travels in the checkpoint); forward() leaves them in self.last_drop_masks and replays given
-        ones (drop_masks=...).  Off, the step issues exactly the launches it issued before the option existed."""
+        ones (drop_masks=...).  Off, the step issues exactly the launches it issued before the option existed.
+        `optimizer`: "adamw" or "lamb" (TRAIN.OPTIMIZER, case-insensitive).  lamb is timm's Lamb: the AdamW update with each
+        parameter tensor's rate scaled by its trust ratio ||w|| / ||u|| where its weight decay is not 0 (everywhere with
+        `always_adapt`), capped at 1 with `trust_clip`; step() describes it.  `eps`: None takes the optimizer's default, 1e-8
+        for adamw (torch.optim.AdamW's), 1e-6 for lamb (timm's)."""
         assert bn in ("frozen", "batch")
+        optimizer = str(optimizer).lower()
+        if optimizer not in OPTIMIZERS:
+            raise NotImplementedError(f"optimizer = {optimizer!r}: one of {OPTIMIZERS}")
+        self.optimizer, self.trust_clip, self.always_adapt = optimizer, bool(trust_clip), bool(always_adapt)
+        if eps is None:
+            eps = OPTIMIZERS[optimizer]
+        self.last_trust_ratio = self.last_param_norm = self.last_update_norm = None
         if drop_path is None:
             drop_path = getattr(model, "drop_path", 0.0)
         if not 0.0 <= float(drop_path or 0.0) < 1.0:
@@ -1042,7 +1056,7 @@ class TrainStep:
         """The tensor table of the optimizer launch: built once, per step only the gradient addresses are re-pointed;
         rebuilt when the set of gradients changes, the optimizer state is replaced or the engine has re-packed (new copies)."""
         pk_ok = not self.eng.fp8
-        sig = (id(self.eng.tblk[0]["w"].wqkv), pk_ok, id(self.state), self.eng.tensor_identity())
+        sig = (id(self.eng.tblk[0]["w"].wqkv), pk_ok, id(self.state), self.eng.tensor_identity(), self.optimizer, self.always_adapt)
         plan = getattr(self, "_plan", None)
         if plan is not None and plan.sig == sig and len(grads) == plan.ngrads and \
                 all(k in grads and grads[k].dtype == F32 and grads[k].numel() == n for k, n in plan.names.items()):
@@ -1072,7 +1086,11 @@ class TrainStep:
             for lo, n, pk, scale in dests.get(id(p), [(0, p.numel(), None, 1.0)]):
                 items.append((pf[lo:lo + n], g[lo:lo + n], mf[lo:lo + n], vf[lo:lo + n], lr, wd, pk, scale))
                 pieces.append((k, lo))
-        plan = hip.AdamwPlan(items, joined=[lo != 0 for _, lo in pieces])     # the norm's table: one entry per gradient tensor
+        joined = [lo != 0 for _, lo in pieces]                                # the norm's table: one entry per gradient tensor
+        if self.optimizer == "lamb":                                          # (and one trust ratio per entry)
+            plan = hip.LambPlan(items, joined=joined, always_adapt=self.always_adapt)
+        else:
+            plan = hip.AdamwPlan(items, joined=joined)
         plan.sig, plan.pieces, plan.names, plan.ngrads = sig, pieces, names, len(grads)
         plan.rates_for = (self.lr, self.lr_share, self.wd, self.wd_share)
         plan.packs = bool(dests)
@@ -1098,7 +1116,17 @@ class TrainStep:
         (step() never does).  A non-finite norm is not skipped: it reaches the parameters as it does in torch.
         Ranks: the norm is taken after the rank averaging (backward()'s, or world_average=True's), so it is the norm of the
         averaged gradient, identical on every rank, with no further collective.  After accumulate() it is the norm of the SUM
-        over the chunks, which is what a one-shot step on the whole batch clips."""
+        over the chunks, which is what a one-shot step on the whole batch clips.
+
+        optimizer = "lamb": three calls in place of the AdamW launch (msclip_lamb_partials -> msclip_lamb_ratios ->
+        msclip_lamb_apply, include/msclip_ext3.h), behind the two of the clip norm when clip_grad_norm is set and in front of
+        the EMA's: for every Parameter object u = m_hat / (sqrt(v_hat) + eps) + wd * w from the new moments, r = ||w|| / ||u||
+        (1 where either norm is 0 or NaN; min(r, 1) with trust_clip), w -= lr * r * u where wd != 0 or always_adapt, w -= lr * u
+        elsewhere.  The norms are over the whole Parameter (in_proj_weight, two entries of the table, has one ratio) and, like
+        the clip norm, come from parameters and averaged gradients that are identical on every rank: no collective.
+        Afterwards self.last_trust_ratio / last_param_norm / last_update_norm are {parameter name: 0-dim device view}, valid
+        until the next step() and never read back here; last_trust_ratio holds r as computed, also for a tensor whose step
+        did not use it.  They are None under adamw."""
         if self.lr is None:
             raise ValueError("TrainStep.step() needs a learning rate: TrainStep(model, lr=...) or train.from_config(model, config)")
         self._ema_live("step")
@@ -1110,7 +1138,10 @@ class TrainStep:
             if world_average:
                 world_average_(grads)
             plan = self._adamw_plan(grads)
-            plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm)
+            if self.optimizer == "lamb":
+                plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm, trust_clip=self.trust_clip)
+            else:
+                plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm)
             plan.hold = None
             if self._ema is not None:                # behind the AdamW launch on the same stream: the shadows follow the new values
                 self._ema.plan.run(self.ema_decay)
@@ -1119,6 +1150,10 @@ class TrainStep:
             self.last_grad_norm = self.last_clip_coef = None
         else:
             self.last_grad_norm, self.last_clip_coef = plan.norm, plan.coef
+        if self.optimizer == "lamb":
+            order = list(dict.fromkeys(k for k, _ in plan.pieces))             # the table's parameters, in its order
+            self.last_trust_ratio, self.last_param_norm, self.last_update_norm = (
+                {k: row[i] for i, k in enumerate(order)} for row in (plan.ratio, plan.param_norm, plan.update_norm))
         if plan.packs:
             self.eng.repack_after_optimizer()
         else:
@@ -1321,9 +1356,24 @@ def _optimizer_state_dict(ts):
         st = ts.state.get(k)
         if st is not None:
             state[i] = {"step": torch.tensor(float(ts.steps)), "exp_avg": st[0].detach().cpu(), "exp_avg_sq": st[1].detach().cpu()}
+    if getattr(ts, "optimizer", "adamw") == "lamb":       # timm Lamb's group keys; the adamW dict is what it was before lamb existed
+        pgs = [{"lr": lr, "weight_decay": wd, "bias_correction": True, "betas": tuple(ts.betas), "eps": ts.eps, "grad_averaging": True,
+                "max_grad_norm": float(ts.clip_grad_norm) if ts.clip_grad_norm else None, "trust_clip": ts.trust_clip,
+                "always_adapt": ts.always_adapt, "params": idx} for (lr, wd), idx in groups.items()]
+        return {"state": state, "param_groups": pgs,
+                "msclip": {"steps": ts.steps, "bn": ts.bn, "names": list(index), "optimizer": "lamb"}}
     pgs = [{"lr": lr, "weight_decay": wd, "betas": tuple(ts.betas), "eps": ts.eps, "amsgrad": False, "params": idx}
            for (lr, wd), idx in groups.items()]
     return {"state": state, "param_groups": pgs, "msclip": {"steps": ts.steps, "bn": ts.bn, "names": list(index)}}
+
+
+def _check_optimizer_kind(opt, ts, path):
+    """A checkpoint's moments belong to the optimizer that wrote them ('msclip'.'optimizer'; absent: adamw)."""
+    kind = str(opt["msclip"].get("optimizer", "adamw")).lower()
+    mine = getattr(ts, "optimizer", "adamw")
+    if kind != mine:
+        raise ValueError(f"{path} was written by TRAIN.OPTIMIZER {kind!r}, this TrainStep runs {mine!r}: the optimizer "
+                         "state of one is not the other's")
 
 
 def save_checkpoint(model, ts, path, step, model_name="", perf=0.0):
@@ -1353,6 +1403,7 @@ def resume_checkpoint(model, ts, path):
     from .checkpoint import check_aliases, extract_state_dict
     ts._ema_live("resume_checkpoint")
     obj = torch.load(path, map_location="cpu", weights_only=False)
+    _check_optimizer_kind(obj["optimizer"], ts, path)    # (before anything is loaded)
     if ts.ema_shadow is not None and "ema_shadow_states" not in obj:
         raise KeyError(f"{path} has no 'ema_shadow_states': it was written without TRAIN.EMA_DECAY, this TrainStep has "
                        f"ema_decay = {ts.ema_decay}")
@@ -1382,16 +1433,18 @@ def resume_checkpoint(model, ts, path):
 
 def from_config(model, config, bn="batch", drop_path_mode="sample"):
     """TrainStep with the reference yaml's optimizer block (experiments/model/b32.yaml:32-52 + the msclips overlays):
-    TRAIN.OPTIMIZER (only adamW is implemented: anything else raises), TRAIN.LR / WD / WITHOUT_WD_LIST, TRAIN.OPTIMIZER_ARGS
+    TRAIN.OPTIMIZER (adamW, or lamb / timm with OPTIMIZER_ARGS.opt lamb -- optimizer_settings; anything else raises), TRAIN.LR / WD / WITHOUT_WD_LIST, TRAIN.OPTIMIZER_ARGS
     (betas / eps; absent => torch.optim.AdamW's defaults, what `AdamW(params, lr=..., weight_decay=..., **{})` gives),
     CUSTOM.LR_SHARE / WD_SHARE for the modality-shared tensors (already scaled with the world size by update_config,
     lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off), TRAIN.EMA_DECAY
     (shadow weights updated inside step(); absent or 0.0 = off), MODEL.SPEC.VISION.DROP_PATH (stochastic depth on the vision
     blocks, one draw per image per branch unless drop_path_mode says "position"; absent or 0.0 = off).
     bn = "batch" (default): train-mode BatchNorm as the reference's modules run in train(); "frozen": running statistics."""
+    settings = optimizer_settings(config)
     ts = TrainStep(model, bn=bn, ema_decay=ema_setting(config), drop_path=drop_path_setting(config), drop_path_mode=drop_path_mode,
-                   **optimizer_settings(config))
-    ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
+                   **settings)
+    if "clip_grad_norm" not in settings:             # (lamb: already settled between CLIP_GRAD_NORM and OPTIMIZER_ARGS.max_grad_norm)
+        ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
     ts.schedule = lr_schedule(config)            # TRAIN.LR_SCHEDULER of the yaml (None when the config has none)
     return ts
 
@@ -1482,17 +1535,53 @@ def drop_path_table(keep_draws, Bi, Lv, M, mode, keep):
 
 
 def optimizer_settings(config):
-    """The optimizer block of a reference config as TrainStep keyword arguments (needs no GPU)."""
+    """The optimizer block of a reference config as TrainStep keyword arguments (needs no GPU).
+    TRAIN.OPTIMIZER adamW: OPTIMIZER_ARGS betas / eps (torch.optim.AdamW's defaults) and lr (ignored: TRAIN.LR rules).
+    TRAIN.OPTIMIZER lamb, or timm with OPTIMIZER_ARGS.opt lamb (lib/config/default.py:313-314; both case-insensitive): timm
+    Lamb's keys -- betas / opt_betas, eps / opt_eps (default 1e-6), trust_clip, always_adapt, max_grad_norm, and
+    bias_correction / grad_averaging, which must be true.  max_grad_norm becomes clip_grad_norm where TRAIN.CLIP_GRAD_NORM is 0;
+    both set and different is a ValueError; neither means no clipping (timm's own default of 1.0 is NOT applied: the
+    reference's CLIP_GRAD_NORM 0.0 is).  For lamb the result carries optimizer / trust_clip / always_adapt / clip_grad_norm;
+    for adamW it is what it was before lamb existed."""
     tr, cu = config.TRAIN, config.CUSTOM
     opt = str(tr.get("OPTIMIZER", "sgd"))
-    if opt.lower() != "adamw":
-        raise NotImplementedError(f"TRAIN.OPTIMIZER = {opt!r}: this build implements adamW only (the released MS-CLIP-S "
-                                  "configs' optimizer, experiments/model/b32.yaml:48)")
     oa = dict(tr.get("OPTIMIZER_ARGS", None) or {})
-    betas = tuple(oa.pop("betas", (0.9, 0.999)))
-    eps = float(oa.pop("eps", 1e-8))
+    kind = opt.lower()
+    if kind == "timm":
+        kind = str(oa.pop("opt", "")).lower()
+        if kind != "lamb":
+            raise NotImplementedError(f"TRAIN.OPTIMIZER = 'timm' with OPTIMIZER_ARGS.opt = {kind!r}: of timm's optimizers this "
+                                      "build implements lamb only")
+    if kind not in ("adamw", "lamb"):
+        raise NotImplementedError(f"TRAIN.OPTIMIZER = {opt!r}: this build implements adamW (the released MS-CLIP-S configs' "
+                                  "optimizer, experiments/model/b32.yaml:48) and lamb")
+    base = dict(lr=tr.LR, lr_share=cu.get("LR_SHARE", None) or None, wd=tr.WD, wd_share=cu.get("WD_SHARE", None) or None)
+    without_wd = tuple(tr.get("WITHOUT_WD_LIST", ()) or ())
     oa.pop("lr", None)
+    if kind == "adamw":
+        betas = tuple(oa.pop("betas", (0.9, 0.999)))
+        eps = float(oa.pop("eps", 1e-8))
+        if oa:
+            raise NotImplementedError(f"TRAIN.OPTIMIZER_ARGS keys {sorted(oa)} are not implemented")
+        return dict(base, betas=betas, eps=eps, without_wd=without_wd)
+
+    def either(a, b, default):
+        if a in oa and b in oa and oa[a] != oa[b]:
+            raise ValueError(f"TRAIN.OPTIMIZER_ARGS.{a} = {oa[a]!r} and .{b} = {oa[b]!r} disagree")
+        va, vb = oa.pop(a, None), oa.pop(b, None)
+        return default if va is None and vb is None else (vb if va is None else va)
+
+    betas = tuple(either("betas", "opt_betas", (0.9, 0.999)))
+    eps = float(either("eps", "opt_eps", OPTIMIZERS["lamb"]))
+    for key in ("bias_correction", "grad_averaging"):
+        if not bool(oa.pop(key, True)):
+            raise NotImplementedError(f"TRAIN.OPTIMIZER_ARGS.{key} = False is not implemented (lamb runs with both on)")
+    trust_clip, always_adapt = bool(oa.pop("trust_clip", False)), bool(oa.pop("always_adapt", False))
+    own = float(oa.pop("max_grad_norm", 0.0) or 0.0)
+    clip = float(tr.get("CLIP_GRAD_NORM", 0.0) or 0.0)
+    if own and clip and own != clip:
+        raise ValueError(f"TRAIN.CLIP_GRAD_NORM = {clip!r} and TRAIN.OPTIMIZER_ARGS.max_grad_norm = {own!r} disagree: set one")
     if oa:
         raise NotImplementedError(f"TRAIN.OPTIMIZER_ARGS keys {sorted(oa)} are not implemented")
-    return dict(lr=tr.LR, lr_share=cu.get("LR_SHARE", None) or None, wd=tr.WD, wd_share=cu.get("WD_SHARE", None) or None,
-                betas=betas, eps=eps, without_wd=tuple(tr.get("WITHOUT_WD_LIST", ()) or ()))
+    return dict(base, betas=betas, eps=eps, without_wd=without_wd, optimizer="lamb", trust_clip=trust_clip,
+                always_adapt=always_adapt, clip_grad_norm=clip or own)

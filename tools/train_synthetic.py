@@ -2,6 +2,7 @@
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
                                     [--accumulate K] [--clip-grad-norm X] [--ema-decay D] [--drop-path P [--drop-path-mode M]]
+                                    [--optimizer adamw|lamb [--trust-clip]]
 
 --accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
 TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
@@ -15,6 +16,10 @@ inference-path loss is also printed under the shadow weights (TrainStep.ema_weig
 --drop-path P: MODEL.SPEC.VISION.DROP_PATH, stochastic depth on both residual branches of every vision block (masks drawn on
 the device, one draw per image -- or with --drop-path-mode position per token position, as the reference module does).  The
 training losses then carry the masks' noise; the inference-path loss at the end does not.
+
+--optimizer lamb: TRAIN.OPTIMIZER lamb, every parameter tensor's rate scaled by its trust ratio ||w|| / ||u|| inside step() (on
+the device; --trust-clip caps the ratio at 1); every fifth step also prints the smallest and largest ratio of the tensors that
+adapt.  LAMB's rates are larger than AdamW's: try --lr 2e-3.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -51,6 +56,8 @@ def main():
                     help="P in (0, 1): stochastic depth on the vision blocks' residual branches (MODEL.SPEC.VISION.DROP_PATH; 0 = off)")
     ap.add_argument("--drop-path-mode", choices=("sample", "position"), default="sample",
                     help="one draw per image (sample) or per token position, shared by the batch (position: the reference module's layout)")
+    ap.add_argument("--optimizer", choices=("adamw", "lamb"), default="adamw", help="TRAIN.OPTIMIZER (lamb: per-tensor trust ratios)")
+    ap.add_argument("--trust-clip", action="store_true", help="lamb: cap the trust ratio at 1 (OPTIMIZER_ARGS.trust_clip)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -65,7 +72,8 @@ def main():
         from msclip_amd import hip
         hip.use_compute_stream(dev)
     cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm), "TRAIN.EMA_DECAY", str(args.ema_decay),
-                                    "MODEL.SPEC.VISION.DROP_PATH", str(args.drop_path)])
+                                    "MODEL.SPEC.VISION.DROP_PATH", str(args.drop_path)]
+                       + (["TRAIN.OPTIMIZER", "lamb", "TRAIN.OPTIMIZER_ARGS.trust_clip", str(args.trust_clip)] if args.optimizer == "lamb" else []))
     from bench import load_schema
     model = get_clip_model(cfg)
     model.load_state_dict(synth.synth_state_dict(load_schema(args.model), seed=0), strict=True)
@@ -99,6 +107,9 @@ def main():
         note = ""
         if ts.last_grad_norm is not None and step % 5 == 0:   # one more read on a step that has just read the loss
             note = f"  grad norm {ts.last_grad_norm.item():.4g} (clipped to {ts.clip_grad_norm:g})"
+        if ts.last_trust_ratio is not None and step % 5 == 0:
+            adapting = torch.stack([ts.last_trust_ratio[k] for k, _, _, wd in ts.param_groups() if wd != 0.0 or ts.always_adapt])
+            note += f"  trust ratio {adapting.min().item():.3g} .. {adapting.max().item():.3g}"
         if rank == 0:
             print(f"step {step:3d}  loss {losses[-1]:.4f}  {ms:7.1f} ms{note}", flush=True)
     # the inference-path loss gathers features and all-reduces its partial sums (GATHER_TENSORS: True): EVERY rank runs it,
