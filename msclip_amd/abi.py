@@ -1,5 +1,6 @@
-"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.  The extension header
-include/msclip_ext.h (declarations newer than that header's ABI version) is read by the same rules under its own version macro.
+"""The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.  The extension headers
+include/msclip_ext.h, msclip_ext2.h and msclip_ext3.h (declarations newer than that header's ABI version) are read by the same
+rules, each under its own version macro.
 
 The mapping rule, for prototype parameters and struct members alike:
     int -> c_int, float -> c_float, long long -> c_longlong;

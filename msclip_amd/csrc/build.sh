@@ -8,7 +8,11 @@ mkdir -p build
 objs=()
 pids=()
 for f in gemm gemm_small attention qkv_attention attention_bwd backward backward_conv rows conv front loss pack api plan comm optim clip ema; do
-  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ gemm_epilogue.h -nt build/$f.o ] || [ plan.h -nt build/$f.o ] || [ multi_tensor.h -nt build/$f.o ] || [ ../../include/msclip_hip.h -nt build/$f.o ] || [ ../../include/msclip_ext.h -nt build/$f.o ] || [ ../../include/msclip_ext2.h -nt build/$f.o ] || [ ../../include/msclip_ext3.h -nt build/$f.o ]; then
+  stale=0
+  for d in $f.hip common.h gemm_epilogue.h plan.h multi_tensor.h ../../include/msclip_hip.h ../../include/msclip_ext.h ../../include/msclip_ext2.h ../../include/msclip_ext3.h; do
+    if [ ! -f build/$f.o ] || [ $d -nt build/$f.o ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     # no fast-math for pack.hip (tensor algebra that must come out bitwise: IEEE division / square root, no contraction) and clip.hip
     # (NaN / Inf must travel), which is why clip.hip is not part of optim.hip: AdamW's division and sqrtf ARE compiled with fast-math,
     # and moving either across that line changes bits; ema.hip (the EMA's multiply, multiply, add must stay three roundings: no fma)

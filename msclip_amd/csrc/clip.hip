@@ -56,19 +56,35 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const SumsqBatch a, float* _
   if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The fold in double of clip_coef_kernel and lamb_ratios_kernel, sumsq_kernel's tree, N sums at once: s[k] of every thread
+// -> six xor-shuffle steps -> one value per wave in LDS, behind a barrier: -> red, sum k's four values from red[4 k] on.
+// One call per kernel: red is one array per N, a second call would write over the first one's values.
+template <int N>
+__device__ __forceinline__ const double* wave_sums_double(double (&s)[N]) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] += __shfl_xor(s[k], o, 64);
+  __shared__ double red[4 * N];
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[4 * k + (threadIdx.x >> 6)] = s[k];
+  __syncthreads();
+  return red;
+}
+
+// -> (w0 + w1) + (w2 + w3) over the four waves
+__device__ __forceinline__ double sum_of_waves(const double* red) { return (red[0] + red[1]) + (red[2] + red[3]); }
+
 // One workgroup: thread t adds partials t, t + 256, ... in double (a serial fp32 fold over the ~4 600 partials of the B/32 model
-// would by itself allow 3e-4 of relative error), then the same tree as above in double.
+// would by itself allow 3e-4 of relative error), then the tree above.
 __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, long long n, float max_norm,
                                                         float* __restrict__ out) {
-  double s = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  double s[1] = {0.0};
+  for (long long i = threadIdx.x; i < n; i += 256) s[0] += (double)partials[i];
+  const double* red = wave_sums_double(s);
   if (threadIdx.x == 0) {
-    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    const float norm = (float)sqrt(sum_of_waves(red));
     const float c = max_norm / (norm + 1e-6f);               // torch: max_norm / (total_norm + 1e-6), clamped to 1 from above
     out[0] = norm;
     out[1] = c > 1.f ? 1.f : c;                              // (a NaN stays a NaN, as torch.clamp keeps it)
@@ -77,8 +93,8 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
 
 // LAMB's trust ratios (include/msclip_ext3.h; the partials are lamb_partials_kernel's of optim.hip, two per chunk): workgroup k
 // adds parameter k's {sum p^2, sum u^2} over its chunks as clip_coef_kernel adds -- thread t takes chunks t, t + 256, ... in
-// double, then the same tree in double.  In this file because the rule is made of comparisons that a NaN must fail and a
-// division by Inf that must give 0.
+// double, then the same tree.  In this file because the rule is made of comparisons that a NaN must fail and a division by Inf
+// that must give 0.
 __global__ __launch_bounds__(256) void lamb_ratios_kernel(const float* __restrict__ partials, const int* __restrict__ first_chunk,
                                                           int n_params, long long n_chunks, int trust_clip,
                                                           float* __restrict__ out) {
@@ -86,25 +102,14 @@ __global__ __launch_bounds__(256) void lamb_ratios_kernel(const float* __restric
   long long c0 = first_chunk[k], c1 = first_chunk[k + 1];
   c0 = c0 < 0 ? 0 : (c0 > n_chunks ? n_chunks : c0);         // (a table that does not match the partials reads none beyond them)
   c1 = c1 < 0 ? 0 : (c1 > n_chunks ? n_chunks : c1);
-  double sw = 0.0, su = 0.0;
+  double s[2] = {0.0, 0.0};                                  // sum p^2, sum u^2
   for (long long c = c0 + threadIdx.x; c < c1; c += 256) {
-    sw += (double)partials[2 * c];
-    su += (double)partials[2 * c + 1];
+    s[0] += (double)partials[2 * c];
+    s[1] += (double)partials[2 * c + 1];
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    sw += __shfl_xor(sw, o, 64);
-    su += __shfl_xor(su, o, 64);
-  }
-  __shared__ double red[8];
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = sw;
-    red[4 + (threadIdx.x >> 6)] = su;
-  }
-  __syncthreads();
+  const double* red = wave_sums_double(s);
   if (threadIdx.x == 0) {
-    const float wn = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-    const float un = (float)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+    const float wn = (float)sqrt(sum_of_waves(red)), un = (float)sqrt(sum_of_waves(red + 4));
     float r = (wn > 0.f && un > 0.f) ? wn / un : 1.f;        // NaN: both comparisons false; un = Inf: 0
     if (trust_clip && r > 1.f) r = 1.f;
     out[k] = r;

@@ -1,5 +1,5 @@
-// The optimizer phase of the training step: AdamW over all parameter tensors and gradient accumulation over the chunks of
-// TrainStep.accumulate (train.py), each over its 325-406 tensors in a handful of launches (multi_tensor.h).  Streaming, bound
+// The optimizer phase of the training step: AdamW and LAMB over all parameter tensors and gradient accumulation over the chunks
+// of TrainStep.accumulate (train.py), each over its 325-406 tensors in a handful of launches (multi_tensor.h).  Streaming, bound
 // by HBM.  The sum of squares and the coefficient of gradient clipping are in clip.hip, which is compiled without fast-math.
 #include "common.h"
 #include "multi_tensor.h"
@@ -10,13 +10,18 @@
 namespace {
 
 // ---- AdamW (decoupled weight decay), one fused pass per parameter tensor; fp32 states.  One statement of the update with
-// the contractions written out, shared by both kernels: their results are bitwise the same.
-__device__ __forceinline__ void adamw_update(float gi, float& mi, float& vi, float& pi, float lr, float b1, float b2, float eps,
-                                             float wd, float c1, float c2) {
+// the contractions written out, shared by every kernel below: their results are bitwise the same.  adam_direction forms the
+// new moments and u = m_hat / (sqrt(v_hat) + eps) + wd * p, adamw_update steps along it.
+__device__ __forceinline__ float adam_direction(float gi, float& mi, float& vi, float pi, float b1, float b2, float eps, float wd,
+                                                float c1, float c2) {
   mi = __fmaf_rn(b1, mi, (1.f - b1) * gi);
   vi = __fmaf_rn(b2, vi, (1.f - b2) * gi * gi);
-  const float upd = __fmaf_rn(wd, pi, mi * c1 / (sqrtf(vi * c2) + eps));
-  pi = __fmaf_rn(-lr, upd, pi);
+  return __fmaf_rn(wd, pi, mi * c1 / (sqrtf(vi * c2) + eps));
+}
+
+__device__ __forceinline__ void adamw_update(float gi, float& mi, float& vi, float& pi, float lr, float b1, float b2, float eps,
+                                             float wd, float c1, float c2) {
+  pi = __fmaf_rn(-lr, adam_direction(gi, mi, vi, pi, b1, b2, eps, wd, c1, c2), pi);
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -34,32 +39,31 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // ---- the same update over many tensors per launch (multi_tensor.h): 36 x 64 B + 400 x 4 B of kernel arguments
 using AdamwBatch = MtBatch<msclip_adamw_tensor, 36, 400>;
 
-// CLIP (msclip_adamw_multi_clipped): the update sees g[i] * coef[0], the clipping coefficient that msclip_clip_coef left on
-// the device.  The product is ONE fp32 multiply, rounded before the moment updates -- the value torch's clip_grad_norm_ stores
-// back into .grad: the empty asm keeps this file's fast-math from re-associating (1 - b1) * (g * coef) into
-// ((1 - b1) * coef) * g.  CLIP = false: coef is not read.
+// CLIP (msclip_adamw_multi_clipped, the LAMB calls with a coefficient): the update sees g[i] * coef[0], the clipping coefficient
+// that msclip_clip_coef left on the device.  The product is ONE fp32 multiply, rounded before the moment updates -- the value
+// torch's clip_grad_norm_ stores back into .grad: the empty asm keeps this file's fast-math from re-associating
+// (1 - b1) * (g * coef) into ((1 - b1) * coef) * g.  CLIP = false: coef is not read.
 template <bool CLIP>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2,
-                                                          const float* __restrict__ coef_dev) {
-  float coef = 1.f;
-  if constexpr (CLIP) coef = *coef_dev;
-  MT_DECODE_CHUNK(a, t, lo, cnt);
-  float* __restrict__ p = t.p + lo;
-  const float* __restrict__ g = t.g + lo;
-  float* __restrict__ m = t.m + lo;
-  float* __restrict__ v = t.v + lo;
-  const float lr = t.lr, wd = t.weight_decay;
+__device__ __forceinline__ float clipped(float gi, float coef) {
+  if constexpr (CLIP) {
+    gi *= coef;
+    asm volatile("" : "+v"(gi));
+  }
+  return gi;
+}
+
+// The update of one chunk, the body of adamw_multi_kernel and lamb_apply_kernel: 16-byte path where every operand allows it,
+// 4-byte path for the rest.  pkb / pkf: the packed copy of the new values (the engine's GEMM operand) in bf16 or fp32, or both
+// null: same rounding as a cast of the updated tensor.  Operands by value, not the table item by reference, for the reason
+// MT_DECODE_CHUNK is a macro (multi_tensor.h); profiles/optim_dedup_isa.md compares the kernels with their earlier text.
+template <bool CLIP>
+__device__ __forceinline__ void adamw_apply_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, bf16_t* __restrict__ pkb, float* __restrict__ pkf, float ps,
+                                                  int cnt, float lr, float wd, float coef, float b1, float b2, float eps, float c1,
+                                                  float c2) {
   auto upd = [&](float gi, float& mi, float& vi, float& pi) {
-    if constexpr (CLIP) {
-      gi *= coef;
-      asm volatile("" : "+v"(gi));
-    }
-    adamw_update(gi, mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
+    adamw_update(clipped<CLIP>(gi, coef), mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
   };
-  // packed copy of the new values (the engine's GEMM operand): same rounding as a cast of the updated tensor
-  bf16_t* __restrict__ pkb = t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr;
-  float* __restrict__ pkf = t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr;
-  const float ps = t.pk_scale;
   int i0 = 0;
   if (!(((size_t)p | (size_t)g | (size_t)m | (size_t)v | (size_t)pkf) & 15) && !((size_t)pkb & 7)) {
     const int n4 = cnt >> 2;
@@ -87,6 +91,17 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, fl
     if (pkb) pkb[i] = f32_to_bf16(pi * ps);
     if (pkf) pkf[i] = pi * ps;
   }
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2,
+                                                          const float* __restrict__ coef_dev) {
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *coef_dev;
+  MT_DECODE_CHUNK(a, t, lo, cnt);
+  const float lr = t.lr, wd = t.weight_decay;                // (read first: their load then leaves with the item's other loads)
+  adamw_apply_chunk<CLIP>(t.p + lo, t.g + lo, t.m + lo, t.v + lo, t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr,
+                          t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr, t.pk_scale, cnt, lr, wd, coef, b1, b2, eps, c1, c2);
 }
 
 // ---- gradient accumulation: 8 B per element in mode 0 (acc = g), 12 B in mode 1 (acc += g).  One IEEE add per element in
@@ -138,17 +153,9 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const AccumBatch a) {
 // ---- LAMB (include/msclip_ext3.h): a trust ratio ||w|| / ||u|| per parameter tensor scales the rate of the AdamW update.  u
 // exists only inside the update, so the step is two passes over the table: lamb_partials_kernel forms the new moments and u
 // in registers and leaves the sums of p^2 and u^2 of every chunk (16 B read per element), lamb_ratios_kernel (clip.hip) folds
-// them per parameter, lamb_apply_kernel is adamw_multi_kernel with the rate scaled (28 B per element).  The kernels above
-// are not touched: these are kernels of their own on a table of their own.  32 x 72 B + 400 x 4 B of kernel arguments.
+// them per parameter, lamb_apply_kernel runs adamw_multi_kernel's body with the rate scaled (28 B per element).  A table of
+// its own (the item carries its parameter and whether it adapts): 32 x 72 B + 400 x 4 B of kernel arguments.
 using LambBatch = MtBatch<msclip_lamb_tensor, 32, 400>;
-
-// u of adamw_update, the same statements on the same values: the moments are not stored by this pass
-__device__ __forceinline__ float lamb_direction(float gi, float mi, float vi, float pi, float b1, float b2, float eps, float wd,
-                                                float c1, float c2) {
-  mi = __fmaf_rn(b1, mi, (1.f - b1) * gi);
-  vi = __fmaf_rn(b2, vi, (1.f - b2) * gi * gi);
-  return __fmaf_rn(wd, pi, mi * c1 / (sqrtf(vi * c2) + eps));
-}
 
 // a + b as written: this file's fast-math may not re-associate the folds below (the addition order is what the error bound of
 // tests/test_gpu_lamb.py counts, sumsq_kernel's of clip.hip)
@@ -173,12 +180,8 @@ __global__ __launch_bounds__(256) void lamb_partials_kernel(const LambBatch a, f
   const float* __restrict__ m = t.m + lo;
   const float* __restrict__ v = t.v + lo;
   const float wd = t.weight_decay;
-  auto dir = [&](float gi, float mi, float vi, float pi) {
-    if constexpr (CLIP) {
-      gi *= coef;
-      asm volatile("" : "+v"(gi));
-    }
-    return lamb_direction(gi, mi, vi, pi, b1, b2, eps, wd, c1, c2);
+  auto dir = [&](float gi, float mi, float vi, float pi) {   // u of adamw_update on copies of the moments: this pass stores none
+    return adam_direction(clipped<CLIP>(gi, coef), mi, vi, pi, b1, b2, eps, wd, c1, c2);
   };
   float sp[4] = {0.f, 0.f, 0.f, 0.f}, su[4] = {0.f, 0.f, 0.f, 0.f};
   int i0 = 0;
@@ -242,53 +245,86 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(const LambBatch a, floa
   float coef = 1.f;
   if constexpr (CLIP) coef = *coef_dev;
   MT_DECODE_CHUNK(a, t, lo, cnt);
-  float* __restrict__ p = t.p + lo;
-  const float* __restrict__ g = t.g + lo;
-  float* __restrict__ m = t.m + lo;
-  float* __restrict__ v = t.v + lo;
-  float lr = t.lr;
+  float* p = t.p + lo;                                       // (in front of the rate: the item's loads then leave together)
+  const float* g = t.g + lo;
+  float* m = t.m + lo;
+  float* v = t.v + lo;
+  float lr_eff = t.lr;
   if (t.adapt) {
-    lr *= ratio_dev[t.param];
-    asm volatile("" : "+v"(lr));
+    lr_eff *= ratio_dev[t.param];
+    asm volatile("" : "+v"(lr_eff));
   }
-  const float wd = t.weight_decay;
-  auto upd = [&](float gi, float& mi, float& vi, float& pi) {
-    if constexpr (CLIP) {
-      gi *= coef;
-      asm volatile("" : "+v"(gi));
-    }
-    adamw_update(gi, mi, vi, pi, lr, b1, b2, eps, wd, c1, c2);
-  };
-  bf16_t* __restrict__ pkb = t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr;
-  float* __restrict__ pkf = t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr;
-  const float ps = t.pk_scale;
-  int i0 = 0;
-  if (!(((size_t)p | (size_t)g | (size_t)m | (size_t)v | (size_t)pkf) & 15) && !((size_t)pkb & 7)) {
-    const int n4 = cnt >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      const float4 g4 = ((const float4*)g)[i];
-      float4 m4 = ((float4*)m)[i], v4 = ((float4*)v)[i], p4 = ((float4*)p)[i];
-      upd(g4.x, m4.x, v4.x, p4.x);
-      upd(g4.y, m4.y, v4.y, p4.y);
-      upd(g4.z, m4.z, v4.z, p4.z);
-      upd(g4.w, m4.w, v4.w, p4.w);
-      ((float4*)m)[i] = m4;
-      ((float4*)v)[i] = v4;
-      ((float4*)p)[i] = p4;
-      if (pkb) ((uint2*)pkb)[i] = make_uint2(pack_bf16x2(p4.x * ps, p4.y * ps), pack_bf16x2(p4.z * ps, p4.w * ps));
-      if (pkf) ((float4*)pkf)[i] = make_float4(p4.x * ps, p4.y * ps, p4.z * ps, p4.w * ps);
-    }
-    i0 = n4 << 2;
+  adamw_apply_chunk<CLIP>(p, g, m, v, t.pk && !t.pk_f32 ? (bf16_t*)t.pk + lo : nullptr,
+                          t.pk && t.pk_f32 ? (float*)t.pk + lo : nullptr, t.pk_scale, cnt, lr_eff, t.weight_decay, coef, b1, b2, eps,
+                          c1, c2);
+}
+
+// ---- host side, common to the AdamW and the LAMB tables (their items share p, g, m, v, n, pk, pk_f32)
+template <class T>
+void adam_advance(T& t, long long k) {
+  t.p += k;
+  t.g += k;
+  t.m += k;
+  t.v += k;
+  t.n -= k;
+  if (t.pk) t.pk = (char*)t.pk + (size_t)k * (t.pk_f32 ? 4 : 2);
+}
+
+// The bias corrections 1 / (1 - beta^step) of the two moments.  beta^step is powf's in the AdamW calls and repeated squaring
+// (SQUARING, __builtin_powif) in the LAMB calls: what this file's fast-math made of the one expression powf(beta, (float)step)
+// in the two kinds of entry point while each wrote it out, and what each therefore has always computed; the two can differ in
+// the last bit.  Stated here so that neither depends on the code around the call: the empty asm keeps powf a call of powf.
+struct BiasCorrections { float c1, c2; };
+template <bool SQUARING>
+BiasCorrections bias_corrections(float beta1, float beta2, int step) {
+  float fstep = (float)step;
+  asm volatile("" : "+m"(fstep));
+  const float p1 = SQUARING ? __builtin_powif(beta1, step) : powf(beta1, fstep);
+  const float p2 = SQUARING ? __builtin_powif(beta2, step) : powf(beta2, fstep);
+  return {1.f / (1.f - p1), 1.f / (1.f - p2)};
+}
+
+// what every table must satisfy before a kernel may see it; an entry point adds its own conditions
+template <class T>
+bool adam_table_ok(const T* tensors, int count, int step) {
+  if (!tensors || count < 0 || step < 1) return false;
+  for (int i = 0; i < count; ++i) {
+    const T& t = tensors[i];
+    if (!t.p || !t.g || !t.m || !t.v || t.n <= 0 || (t.pk && (t.pk_f32 < 0 || t.pk_f32 > 1))) return false;
   }
-  for (int i = i0 + threadIdx.x; i < cnt; i += 256) {
-    float mi = m[i], vi = v[i], pi = p[i];
-    upd(g[i], mi, vi, pi);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-    if (pkb) pkb[i] = f32_to_bf16(pi * ps);
-    if (pkf) pkf[i] = pi * ps;
+  return true;
+}
+
+// the CLIP instantiation of a kernel: the clipped one where a coefficient is given
+template <class Kernel>
+Kernel pick_clip(const float* coef_dev, Kernel clipped, Kernel plain) {
+  return coef_dev ? clipped : plain;
+}
+
+int adamw_multi_launch(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                       const float* coef_dev, void* stream) {
+  if (!adam_table_ok(tensors, count, step)) return MSCLIP_EINVAL;
+  const BiasCorrections bc = bias_corrections<false>(beta1, beta2, step);
+  const auto kernel = pick_clip(coef_dev, adamw_multi_kernel<true>, adamw_multi_kernel<false>);
+  mt_for_each_launch<AdamwBatch>(tensors, count, adam_advance<msclip_adamw_tensor>, [&](const AdamwBatch& b, int nb, long long) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev);
+  });
+  return msclip_launch_status();
+}
+
+// -> the chunk count of the table, or -1 for a table that no kernel may see
+long long lamb_table_chunks(const msclip_lamb_tensor* tensors, int count, int step, const float* coef_dev) {
+  if (!adam_table_ok(tensors, count, step) || ((size_t)coef_dev & 3)) return -1;
+  long long chunks = 0;
+  for (int i = 0; i < count; ++i) {
+    const msclip_lamb_tensor& t = tensors[i];
+    if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v) & 3) return -1;
+    const int prev = i ? tensors[i - 1].param : -1;          // 0, then the same parameter or the next one
+    if (t.param != prev && t.param != prev + 1) return -1;
+    if (i == 0 && t.param != 0) return -1;
+    chunks += (t.n + MT_CHUNK - 1) / MT_CHUNK;
   }
+  return chunks;
 }
 
 }  // namespace
@@ -297,49 +333,23 @@ extern "C" int msclip_adamw(float* p, const float* g, float* m, float* v, long l
                             float eps, float weight_decay, int step, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_adamw, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step);
   if (!p || !g || !m || !v || n <= 0 || step < 1) return MSCLIP_EINVAL;
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
+  const BiasCorrections bc = bias_corrections<false>(beta1, beta2, step);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for((size_t)n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (size_t)n,
-                     lr, beta1, beta2, eps, weight_decay, c1, c2);
-  return msclip_launch_status();
-}
-
-template <bool CLIP>
-static int adamw_multi_launch(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
-                              const float* coef_dev, void* stream) {
-  if (!tensors || count < 0 || step < 1) return MSCLIP_EINVAL;
-  for (int i = 0; i < count; ++i)
-    if (!tensors[i].p || !tensors[i].g || !tensors[i].m || !tensors[i].v || tensors[i].n <= 0 ||
-        (tensors[i].pk && (tensors[i].pk_f32 < 0 || tensors[i].pk_f32 > 1)))
-      return MSCLIP_EINVAL;
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
-  mt_for_each_launch<AdamwBatch>(
-      tensors, count,
-      [](msclip_adamw_tensor& t, long long k) {
-        t.p += k;
-        t.g += k;
-        t.m += k;
-        t.v += k;
-        t.n -= k;
-        if (t.pk) t.pk = (char*)t.pk + (size_t)k * (t.pk_f32 ? 4 : 2);
-      },
-      [&](const AdamwBatch& b, int nb, long long) {
-        hipLaunchKernelGGL(adamw_multi_kernel<CLIP>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                           coef_dev);
-      });
+                     lr, beta1, beta2, eps, weight_decay, bc.c1, bc.c2);
   return msclip_launch_status();
 }
 
 extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
                                   void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi);
-  return adamw_multi_launch<false>(tensors, count, beta1, beta2, eps, step, nullptr, stream);
+  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, nullptr, stream);
 }
 
 extern "C" int msclip_adamw_multi_clipped(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps,
                                           int step, const float* coef_dev, void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi_clipped);
   if (!coef_dev || ((size_t)coef_dev & 3)) return MSCLIP_EINVAL;
-  return adamw_multi_launch<true>(tensors, count, beta1, beta2, eps, step, coef_dev, stream);
+  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, coef_dev, stream);
 }
 
 extern "C" int msclip_grad_accumulate(const msclip_accum_tensor* tensors, int count, int mode, void* stream) {
@@ -362,32 +372,6 @@ extern "C" int msclip_grad_accumulate(const msclip_accum_tensor* tensors, int co
   return msclip_launch_status();
 }
 
-// ---- LAMB
-static void lamb_advance(msclip_lamb_tensor& t, long long k) {
-  t.p += k;
-  t.g += k;
-  t.m += k;
-  t.v += k;
-  t.n -= k;
-  if (t.pk) t.pk = (char*)t.pk + (size_t)k * (t.pk_f32 ? 4 : 2);
-}
-
-// -> the chunk count of the table, or -1 for a table that no kernel may see
-static long long lamb_table_chunks(const msclip_lamb_tensor* tensors, int count, int step, const float* coef_dev) {
-  if (!tensors || count < 0 || step < 1 || ((size_t)coef_dev & 3)) return -1;
-  long long chunks = 0;
-  for (int i = 0; i < count; ++i) {
-    const msclip_lamb_tensor& t = tensors[i];
-    if (!t.p || !t.g || !t.m || !t.v || t.n <= 0 || (t.pk && (t.pk_f32 < 0 || t.pk_f32 > 1))) return -1;
-    if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v) & 3) return -1;
-    const int prev = i ? tensors[i - 1].param : -1;          // 0, then the same parameter or the next one
-    if (t.param != prev && t.param != prev + 1) return -1;
-    if (i == 0 && t.param != 0) return -1;
-    chunks += (t.n + MT_CHUNK - 1) / MT_CHUNK;
-  }
-  return chunks;
-}
-
 extern "C" int msclip_ext3_abi_version(void) { return MSCLIP_EXT3_ABI_VERSION; }
 
 extern "C" int msclip_lamb_partials(const msclip_lamb_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
@@ -396,14 +380,11 @@ extern "C" int msclip_lamb_partials(const msclip_lamb_tensor* tensors, int count
   const long long chunks = lamb_table_chunks(tensors, count, step, coef_dev);
   if (chunks < 0 || !partials || ((size_t)partials & 3)) return MSCLIP_EINVAL;
   if (n_partials != 2 * chunks) return MSCLIP_EINVAL;        // every slot the fold will read is written, none beyond the array
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
-  mt_for_each_launch<LambBatch>(tensors, count, lamb_advance, [&](const LambBatch& b, int nb, long long first_chunk) {
-    if (coef_dev)
-      hipLaunchKernelGGL(lamb_partials_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                         coef_dev, partials + 2 * first_chunk);
-    else
-      hipLaunchKernelGGL(lamb_partials_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                         coef_dev, partials + 2 * first_chunk);
+  const BiasCorrections bc = bias_corrections<true>(beta1, beta2, step);
+  const auto kernel = pick_clip(coef_dev, lamb_partials_kernel<true>, lamb_partials_kernel<false>);
+  mt_for_each_launch<LambBatch>(tensors, count, adam_advance<msclip_lamb_tensor>, [&](const LambBatch& b, int nb, long long first) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev,
+                       partials + 2 * first);
   });
   return msclip_launch_status();
 }
@@ -412,14 +393,10 @@ extern "C" int msclip_lamb_apply(const msclip_lamb_tensor* tensors, int count, f
                                  const float* coef_dev, const float* ratio_dev, void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_lamb_apply);
   if (lamb_table_chunks(tensors, count, step, coef_dev) < 0 || !ratio_dev || ((size_t)ratio_dev & 3)) return MSCLIP_EINVAL;
-  const float c1 = 1.f / (1.f - powf(beta1, (float)step)), c2 = 1.f / (1.f - powf(beta2, (float)step));
-  mt_for_each_launch<LambBatch>(tensors, count, lamb_advance, [&](const LambBatch& b, int nb, long long) {
-    if (coef_dev)
-      hipLaunchKernelGGL(lamb_apply_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                         coef_dev, ratio_dev);
-    else
-      hipLaunchKernelGGL(lamb_apply_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, c1, c2,
-                         coef_dev, ratio_dev);
+  const BiasCorrections bc = bias_corrections<true>(beta1, beta2, step);
+  const auto kernel = pick_clip(coef_dev, lamb_apply_kernel<true>, lamb_apply_kernel<false>);
+  mt_for_each_launch<LambBatch>(tensors, count, adam_advance<msclip_lamb_tensor>, [&](const LambBatch& b, int nb, long long) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev, ratio_dev);
   });
   return msclip_launch_status();
 }

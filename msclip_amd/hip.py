@@ -8,6 +8,7 @@ library is missing or no GPU is visible.
 import ctypes
 import os
 import subprocess
+import sys
 
 import torch
 
@@ -16,28 +17,28 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSCLIP_HIP_LIB") or os.path.join(_HERE, "csrc", "libmsclip_hip.so")   # override: kernel A/B probes only
 INT_MAX = 2 ** 31 - 1
-_ABI = abi.load()                                        # include/msclip_hip.h, read once: the only statement of the C ABI
-ABI_VERSION = _ABI.version
-EXPORTS = tuple(_ABI.protos)
+# The headers, each read once.  include/msclip_hip.h is the statement of the C ABI; the extension headers hold the declarations
+# newer than ABI_VERSION, each a table of its own, so that _ABI / EXPORTS / ABI_VERSION keep describing msclip_hip.h alone: the
+# weight EMA, the row-scale entry points (stochastic depth) and LAMB, the last two pointing to structs of msclip_hip.h.
+_ABI = abi.load()
+_EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
+_EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
+_EXT3 = abi.load(abi.EXT3_HEADER, abi.EXT3_VERSION_MACRO, known=tuple(_ABI.structs))
+ABI_VERSION, EXT_ABI_VERSION, EXT2_ABI_VERSION, EXT3_ABI_VERSION = (t.version for t in (_ABI, _EXT, _EXT2, _EXT3))
+# What lib() binds and verifies, one row per header: (attribute of the table above, attribute of its version, header, the
+# library's version function, what a refusal calls the version).  By attribute name: lib() takes both as they are when it runs.
+_BOUND = (
+    ("_ABI", "ABI_VERSION", abi.HEADER, "msclip_abi_version", "ABI"),
+    ("_EXT", "EXT_ABI_VERSION", abi.EXT_HEADER, "msclip_ext_abi_version", "extension ABI"),
+    ("_EXT2", "EXT2_ABI_VERSION", abi.EXT2_HEADER, "msclip_ext2_abi_version", "row-scale extension ABI"),
+    ("_EXT3", "EXT3_ABI_VERSION", abi.EXT3_HEADER, "msclip_ext3_abi_version", "LAMB extension ABI"),
+)
+EXPORTS, EXT_EXPORTS, EXT2_EXPORTS, EXT3_EXPORTS = (tuple(t.protos) for t in (_ABI, _EXT, _EXT2, _EXT3))
 (GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor, SumsqTensor, AccumTensor) = (
     _ABI.structs[n] for n in (
         "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item",
         "msclip_transpose_item", "msclip_adamw_tensor", "msclip_sumsq_tensor", "msclip_accum_tensor"))
-# include/msclip_ext.h, the declarations newer than ABI_VERSION (folded into msclip_hip.h by the next ABI clean-up): a second table,
-# so that _ABI / EXPORTS / ABI_VERSION keep describing msclip_hip.h alone
-_EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
-EXT_ABI_VERSION = _EXT.version
-EXT_EXPORTS = tuple(_EXT.protos)
-EmaTensor = _EXT.structs["msclip_ema_tensor"]
-# include/msclip_ext2.h: the row-scale entry points (stochastic depth), a third table for the same reason
-_EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
-EXT2_ABI_VERSION = _EXT2.version
-EXT2_EXPORTS = tuple(_EXT2.protos)
-# include/msclip_ext3.h: the LAMB entry points (TRAIN.OPTIMIZER lamb), a fourth table
-_EXT3 = abi.load(abi.EXT3_HEADER, abi.EXT3_VERSION_MACRO, known=tuple(_ABI.structs))
-EXT3_ABI_VERSION = _EXT3.version
-EXT3_EXPORTS = tuple(_EXT3.protos)
-LambTensor = _EXT3.structs["msclip_lamb_tensor"]
+EmaTensor, LambTensor = _EXT.structs["msclip_ema_tensor"], _EXT3.structs["msclip_lamb_tensor"]
 CLIP_CHUNK = 32768                                       # elements per partial of msclip_grad_sumsq
 
 
@@ -72,42 +73,19 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise HipUnavailable(f"{LIB_PATH} is missing: run msclip_amd/csrc/build.sh (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _ABI.protos.items():              # abi.py states the C type -> ctypes rule
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_hip.h declares: rebuild "
+        me = sys.modules[__name__]
+        for table, version, path, version_fn, what in _BOUND:
+            header = "include/" + os.path.basename(path)
+            for name, (restype, argtypes) in getattr(me, table).protos.items():    # abi.py states the C type -> ctypes rule
+                fn = getattr(L, name, None)
+                if fn is None:
+                    raise HipUnavailable(f"{LIB_PATH} does not export {name}, which {header} declares: rebuild "
+                                         "(bash msclip_amd/csrc/build.sh)")
+                fn.restype, fn.argtypes = restype, argtypes
+            have, want = getattr(L, version_fn)(), getattr(me, version)
+            if have != want:                               # a stale build of the library (the struct layouts / entry points moved on)
+                raise HipUnavailable(f"{LIB_PATH} has {what} version {have}, this binding needs {want}: rebuild "
                                      "(bash msclip_amd/csrc/build.sh)")
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.msclip_abi_version() != ABI_VERSION:          # a stale build of the library (the struct layouts / entry points moved on)
-            raise HipUnavailable(f"{LIB_PATH} has ABI version {L.msclip_abi_version()}, this binding needs {ABI_VERSION}: rebuild "
-                                 "(bash msclip_amd/csrc/build.sh)")
-        for name, (restype, argtypes) in _EXT.protos.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext.h declares: rebuild "
-                                     "(bash msclip_amd/csrc/build.sh)")
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.msclip_ext_abi_version() != EXT_ABI_VERSION:
-            raise HipUnavailable(f"{LIB_PATH} has extension ABI version {L.msclip_ext_abi_version()}, this binding needs "
-                                 f"{EXT_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
-        for name, (restype, argtypes) in _EXT2.protos.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext2.h declares: rebuild "
-                                     "(bash msclip_amd/csrc/build.sh)")
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.msclip_ext2_abi_version() != EXT2_ABI_VERSION:
-            raise HipUnavailable(f"{LIB_PATH} has row-scale extension ABI version {L.msclip_ext2_abi_version()}, this binding needs "
-                                 f"{EXT2_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
-        for name, (restype, argtypes) in _EXT3.protos.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipUnavailable(f"{LIB_PATH} does not export {name}, which include/msclip_ext3.h declares: rebuild "
-                                     "(bash msclip_amd/csrc/build.sh)")
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.msclip_ext3_abi_version() != EXT3_ABI_VERSION:
-            raise HipUnavailable(f"{LIB_PATH} has LAMB extension ABI version {L.msclip_ext3_abi_version()}, this binding needs "
-                                 f"{EXT3_ABI_VERSION}: rebuild (bash msclip_amd/csrc/build.sh)")
         _lib = L
     return _lib
 
@@ -1841,14 +1819,21 @@ class AdamwPlan:
         if not self.n:
             return
         with torch.cuda.device(self.device):
-            if max_norm is None:
-                _check(lib().msclip_adamw_multi(self.arr, self.n, beta1, beta2, eps, step, _stream()), "msclip_adamw_multi")
-                return
             L, st = lib(), _stream()
-            _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
-            _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
-            coef = ctypes.c_void_p(self.clip.data_ptr() + 4)
-            _check(L.msclip_adamw_multi_clipped(self.arr, self.n, beta1, beta2, eps, step, coef, st), "msclip_adamw_multi_clipped")
+            coef = self._clip_coef(L, st, max_norm)
+            if coef is None:
+                _check(L.msclip_adamw_multi(self.arr, self.n, beta1, beta2, eps, step, st), "msclip_adamw_multi")
+            else:
+                _check(L.msclip_adamw_multi_clipped(self.arr, self.n, beta1, beta2, eps, step, coef, st), "msclip_adamw_multi_clipped")
+
+    def _clip_coef(self, L, st, max_norm):
+        """The clip prologue of run(): msclip_grad_sumsq -> msclip_clip_coef on stream `st`, -> the device address of coef; None,
+        and nothing issued, where max_norm is None."""
+        if max_norm is None:
+            return None
+        _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
+        _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
+        return ctypes.c_void_p(self.clip.data_ptr() + 4)
 
 
 class LambPlan(AdamwPlan):
@@ -1890,11 +1875,7 @@ class LambPlan(AdamwPlan):
             return
         with torch.cuda.device(self.device):
             L, st = lib(), _stream()
-            coef = None
-            if max_norm is not None:
-                _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
-                _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
-                coef = ctypes.c_void_p(self.clip.data_ptr() + 4)
+            coef = self._clip_coef(L, st, max_norm)
             _check(L.msclip_lamb_partials(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.lamb_partials),
                                           2 * self.n_chunks, st), "msclip_lamb_partials")
             _check(L.msclip_lamb_ratios(_p(self.lamb_partials), _p(self.first_chunk), self.n_params, self.n_chunks,

@@ -79,6 +79,7 @@ class TrainStep:
         if optimizer not in OPTIMIZERS:
             raise NotImplementedError(f"optimizer = {optimizer!r}: one of {OPTIMIZERS}")
         self.optimizer, self.trust_clip, self.always_adapt = optimizer, bool(trust_clip), bool(always_adapt)
+        self._run_options = {"trust_clip": self.trust_clip} if optimizer == "lamb" else {}      # of the optimizer table's run()
         if eps is None:
             eps = OPTIMIZERS[optimizer]
         self.last_trust_ratio = self.last_param_norm = self.last_update_norm = None
@@ -1138,10 +1139,7 @@ class TrainStep:
             if world_average:
                 world_average_(grads)
             plan = self._adamw_plan(grads)
-            if self.optimizer == "lamb":
-                plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm, trust_clip=self.trust_clip)
-            else:
-                plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm)
+            plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm, **self._run_options)
             plan.hold = None
             if self._ema is not None:                # behind the AdamW launch on the same stream: the shadows follow the new values
                 self._ema.plan.run(self.ema_decay)
