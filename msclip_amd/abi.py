@@ -1,5 +1,5 @@
 """The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.  The extension headers
-include/msclip_ext.h, msclip_ext2.h and msclip_ext3.h (declarations newer than that header's ABI version) are read by the same
+include/msclip_ext.h, msclip_ext2.h, msclip_ext3.h and msclip_ext4.h (declarations newer than that header's ABI version) are read by the same
 rules, each under its own version macro.
 
 The mapping rule, for prototype parameters and struct members alike:
@@ -29,6 +29,10 @@ EXT2_VERSION_MACRO = "MSCLIP_EXT2_ABI_VERSION"
 # the third extension header (the LAMB entry points and their table item), read like the second
 EXT3_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext3.h")
 EXT3_VERSION_MACRO = "MSCLIP_EXT3_ABI_VERSION"
+# the fourth extension header (the non-finite guard of the optimizer phase): its prototypes point to msclip_adamw_tensor of
+# msclip_hip.h and to msclip_lamb_tensor of the third, so it is read with both headers' names known
+EXT4_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext4.h")
+EXT4_VERSION_MACRO = "MSCLIP_EXT4_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 

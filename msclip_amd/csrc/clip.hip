@@ -9,6 +9,7 @@
 #include "plan.h"
 #include "../../include/msclip_hip.h"
 #include "../../include/msclip_ext3.h"
+#include "../../include/msclip_ext4.h"
 
 namespace {
 
@@ -77,11 +78,52 @@ __device__ __forceinline__ const double* wave_sums_double(double (&s)[N]) {
 __device__ __forceinline__ double sum_of_waves(const double* red) { return (red[0] + red[1]) + (red[2] + red[3]); }
 
 // One workgroup: thread t adds partials t, t + 256, ... in double (a serial fp32 fold over the ~4 600 partials of the B/32 model
-// would by itself allow 3e-4 of relative error), then the tree above.
+// would by itself allow 3e-4 of relative error), then the tree above.  GUARD = false is msclip_clip_coef's kernel: `state` is not
+// read, and the instructions are those the kernel had before the parameter existed (the kernel itself is the template: the body
+// as an inlined helper moved one instruction, profiles/nonfinite_guard_isa.md).  GUARD (msclip_clip_coef_guarded,
+// include/msclip_ext4.h): the same fold and the same {total_norm, coef}, plus the verdict on the partials in state[0..4).
+// Non-finite is read off the bit pattern (exponent field all ones), so the verdict does not depend on what a compiler flag makes
+// of a floating-point comparison.  The count and the smallest index travel through a tree of their own (ints: sum and min) in
+// front of the doubles'; state is written by thread 0 alone, state[1] read and written in stream order -- one workgroup, no
+// atomics.
+template <bool GUARD>
 __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, long long n, float max_norm,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, int* __restrict__ state) {
   double s[1] = {0.0};
-  for (long long i = threadIdx.x; i < n; i += 256) s[0] += (double)partials[i];
+  int bad = 0, first = 0x7fffffff;
+  for (long long i = threadIdx.x; i < n; i += 256) {
+    s[0] += (double)partials[i];
+    if constexpr (GUARD) {
+      if ((__float_as_uint(partials[i]) & 0x7f800000u) == 0x7f800000u) {
+        if (!bad) first = i < 0x7fffffff ? (int)i : 0x7fffffff;    // (a thread's indices grow: its first one is its smallest)
+        ++bad;
+      }
+    }
+  }
+  if constexpr (GUARD) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      bad += __shfl_xor(bad, o, 64);
+      const int other = __shfl_xor(first, o, 64);
+      first = other < first ? other : first;
+    }
+    __shared__ int verdict[8];
+    if ((threadIdx.x & 63) == 0) {
+      verdict[threadIdx.x >> 6] = bad;
+      verdict[4 + (threadIdx.x >> 6)] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int count = (verdict[0] + verdict[1]) + (verdict[2] + verdict[3]);
+      int lo = verdict[4];
+      for (int w = 5; w < 8; ++w) lo = verdict[w] < lo ? verdict[w] : lo;
+      const int skip = count != 0;
+      state[0] = skip;
+      state[1] += skip;
+      state[2] = skip ? lo : -1;
+      state[3] = count;
+    }
+  }
   const double* red = wave_sums_double(s);
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(sum_of_waves(red));
@@ -145,7 +187,15 @@ extern "C" int msclip_grad_sumsq(const msclip_sumsq_tensor* tensors, int count, 
 extern "C" int msclip_clip_coef(const float* partials, long long n, float max_norm, float* out, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_clip_coef, stream, partials, n, max_norm, out);
   if (!partials || !out || n <= 0 || !(max_norm >= 0.f) || (((size_t)partials | (size_t)out) & 3)) return MSCLIP_EINVAL;
-  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out);
+  hipLaunchKernelGGL(clip_coef_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out, (int*)nullptr);
+  return msclip_launch_status();
+}
+
+extern "C" int msclip_clip_coef_guarded(const float* partials, long long n, float max_norm, float* out, int* state, void* stream) {
+  MSCLIP_PLAN_HOOK(msclip_clip_coef_guarded, stream, partials, n, max_norm, out, state);
+  if (!partials || !out || !state || n <= 0 || !(max_norm >= 0.f) || (((size_t)partials | (size_t)out | (size_t)state) & 3))
+    return MSCLIP_EINVAL;
+  hipLaunchKernelGGL(clip_coef_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out, state);
   return msclip_launch_status();
 }
 

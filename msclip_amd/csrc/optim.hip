@@ -6,6 +6,7 @@
 #include "plan.h"
 #include "../../include/msclip_hip.h"
 #include "../../include/msclip_ext3.h"
+#include "../../include/msclip_ext4.h"
 
 namespace {
 
@@ -93,9 +94,15 @@ __device__ __forceinline__ void adamw_apply_chunk(float* __restrict__ p, const f
   }
 }
 
-template <bool CLIP>
+// GUARD (include/msclip_ext4.h): every workgroup reads the verdict skip_dev[0] of msclip_clip_coef_guarded once, a uniform read
+// at its head, and leaves where it is not 0 -- a skipped step writes no p, m, v and no packed copy.  GUARD = false: skip_dev is
+// not read, and the kernel is the one it was before the parameter existed (profiles/nonfinite_guard_isa.md).
+template <bool CLIP, bool GUARD>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwBatch a, float b1, float b2, float eps, float c1, float c2,
-                                                          const float* __restrict__ coef_dev) {
+                                                          const float* __restrict__ coef_dev, const int* __restrict__ skip_dev) {
+  if constexpr (GUARD) {
+    if (*skip_dev) return;
+  }
   float coef = 1.f;
   if constexpr (CLIP) coef = *coef_dev;
   MT_DECODE_CHUNK(a, t, lo, cnt);
@@ -239,9 +246,14 @@ __global__ __launch_bounds__(256) void lamb_partials_kernel(const LambBatch a, f
 
 // adamw_multi_kernel with the item's rate scaled by its parameter's trust ratio: lr_eff is ONE fp32 multiply, rounded -- the
 // empty asm keeps fast-math from folding it into the update -- and adamw_update sees it as its lr.
-template <bool CLIP>
+// GUARD: as in adamw_multi_kernel.
+template <bool CLIP, bool GUARD>
 __global__ __launch_bounds__(256) void lamb_apply_kernel(const LambBatch a, float b1, float b2, float eps, float c1, float c2,
-                                                         const float* __restrict__ coef_dev, const float* __restrict__ ratio_dev) {
+                                                         const float* __restrict__ coef_dev, const float* __restrict__ ratio_dev,
+                                                         const int* __restrict__ skip_dev) {
+  if constexpr (GUARD) {
+    if (*skip_dev) return;
+  }
   float coef = 1.f;
   if constexpr (CLIP) coef = *coef_dev;
   MT_DECODE_CHUNK(a, t, lo, cnt);
@@ -301,13 +313,27 @@ Kernel pick_clip(const float* coef_dev, Kernel clipped, Kernel plain) {
   return coef_dev ? clipped : plain;
 }
 
+// skip_dev: NULL, or the verdict of the guarded entry points (include/msclip_ext4.h); every launch of the call is handed it
 int adamw_multi_launch(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
-                       const float* coef_dev, void* stream) {
+                       const float* coef_dev, const int* skip_dev, void* stream) {
   if (!adam_table_ok(tensors, count, step)) return MSCLIP_EINVAL;
   const BiasCorrections bc = bias_corrections<false>(beta1, beta2, step);
-  const auto kernel = pick_clip(coef_dev, adamw_multi_kernel<true>, adamw_multi_kernel<false>);
+  const auto kernel = skip_dev ? pick_clip(coef_dev, adamw_multi_kernel<true, true>, adamw_multi_kernel<false, true>)
+                               : pick_clip(coef_dev, adamw_multi_kernel<true, false>, adamw_multi_kernel<false, false>);
   mt_for_each_launch<AdamwBatch>(tensors, count, adam_advance<msclip_adamw_tensor>, [&](const AdamwBatch& b, int nb, long long) {
-    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev, skip_dev);
+  });
+  return msclip_launch_status();
+}
+
+int lamb_apply_launch(const msclip_lamb_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                      const float* coef_dev, const float* ratio_dev, const int* skip_dev, void* stream) {
+  const BiasCorrections bc = bias_corrections<true>(beta1, beta2, step);
+  const auto kernel = skip_dev ? pick_clip(coef_dev, lamb_apply_kernel<true, true>, lamb_apply_kernel<false, true>)
+                               : pick_clip(coef_dev, lamb_apply_kernel<true, false>, lamb_apply_kernel<false, false>);
+  mt_for_each_launch<LambBatch>(tensors, count, adam_advance<msclip_lamb_tensor>, [&](const LambBatch& b, int nb, long long) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev, ratio_dev,
+                       skip_dev);
   });
   return msclip_launch_status();
 }
@@ -342,14 +368,21 @@ extern "C" int msclip_adamw(float* p, const float* g, float* m, float* v, long l
 extern "C" int msclip_adamw_multi(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
                                   void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi);
-  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, nullptr, stream);
+  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, nullptr, nullptr, stream);
 }
 
 extern "C" int msclip_adamw_multi_clipped(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps,
                                           int step, const float* coef_dev, void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi_clipped);
   if (!coef_dev || ((size_t)coef_dev & 3)) return MSCLIP_EINVAL;
-  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, coef_dev, stream);
+  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, coef_dev, nullptr, stream);
+}
+
+extern "C" int msclip_adamw_multi_guarded(const msclip_adamw_tensor* tensors, int count, float beta1, float beta2, float eps,
+                                          int step, const float* coef_dev, const int* skip_dev, void* stream) {
+  MSCLIP_PLAN_UNSUPPORTED(msclip_adamw_multi_guarded);
+  if (!skip_dev || (((size_t)skip_dev | (size_t)coef_dev) & 3)) return MSCLIP_EINVAL;
+  return adamw_multi_launch(tensors, count, beta1, beta2, eps, step, coef_dev, skip_dev, stream);
 }
 
 extern "C" int msclip_grad_accumulate(const msclip_accum_tensor* tensors, int count, int mode, void* stream) {
@@ -393,10 +426,15 @@ extern "C" int msclip_lamb_apply(const msclip_lamb_tensor* tensors, int count, f
                                  const float* coef_dev, const float* ratio_dev, void* stream) {
   MSCLIP_PLAN_UNSUPPORTED(msclip_lamb_apply);
   if (lamb_table_chunks(tensors, count, step, coef_dev) < 0 || !ratio_dev || ((size_t)ratio_dev & 3)) return MSCLIP_EINVAL;
-  const BiasCorrections bc = bias_corrections<true>(beta1, beta2, step);
-  const auto kernel = pick_clip(coef_dev, lamb_apply_kernel<true>, lamb_apply_kernel<false>);
-  mt_for_each_launch<LambBatch>(tensors, count, adam_advance<msclip_lamb_tensor>, [&](const LambBatch& b, int nb, long long) {
-    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, b, beta1, beta2, eps, bc.c1, bc.c2, coef_dev, ratio_dev);
-  });
-  return msclip_launch_status();
+  return lamb_apply_launch(tensors, count, beta1, beta2, eps, step, coef_dev, ratio_dev, nullptr, stream);
+}
+
+extern "C" int msclip_ext4_abi_version(void) { return MSCLIP_EXT4_ABI_VERSION; }
+
+extern "C" int msclip_lamb_apply_guarded(const msclip_lamb_tensor* tensors, int count, float beta1, float beta2, float eps, int step,
+                                         const float* coef_dev, const float* ratio_dev, const int* skip_dev, void* stream) {
+  MSCLIP_PLAN_UNSUPPORTED(msclip_lamb_apply_guarded);
+  if (lamb_table_chunks(tensors, count, step, coef_dev) < 0 || !ratio_dev || !skip_dev || (((size_t)ratio_dev | (size_t)skip_dev) & 3))
+    return MSCLIP_EINVAL;
+  return lamb_apply_launch(tensors, count, beta1, beta2, eps, step, coef_dev, ratio_dev, skip_dev, stream);
 }

@@ -19,12 +19,15 @@ LIB_PATH = os.environ.get("MSCLIP_HIP_LIB") or os.path.join(_HERE, "csrc", "libm
 INT_MAX = 2 ** 31 - 1
 # The headers, each read once.  include/msclip_hip.h is the statement of the C ABI; the extension headers hold the declarations
 # newer than ABI_VERSION, each a table of its own, so that _ABI / EXPORTS / ABI_VERSION keep describing msclip_hip.h alone: the
-# weight EMA, the row-scale entry points (stochastic depth) and LAMB, the last two pointing to structs of msclip_hip.h.
+# weight EMA, the row-scale entry points (stochastic depth), LAMB and the non-finite guard, the last three pointing to structs of
+# msclip_hip.h (the guard also to LAMB's).
 _ABI = abi.load()
 _EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
 _EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
 _EXT3 = abi.load(abi.EXT3_HEADER, abi.EXT3_VERSION_MACRO, known=tuple(_ABI.structs))
+_EXT4 = abi.load(abi.EXT4_HEADER, abi.EXT4_VERSION_MACRO, known=tuple(_ABI.structs) + tuple(_EXT3.structs))
 ABI_VERSION, EXT_ABI_VERSION, EXT2_ABI_VERSION, EXT3_ABI_VERSION = (t.version for t in (_ABI, _EXT, _EXT2, _EXT3))
+EXT4_ABI_VERSION = _EXT4.version
 # What lib() binds and verifies, one row per header: (attribute of the table above, attribute of its version, header, the
 # library's version function, what a refusal calls the version).  By attribute name: lib() takes both as they are when it runs.
 _BOUND = (
@@ -32,8 +35,10 @@ _BOUND = (
     ("_EXT", "EXT_ABI_VERSION", abi.EXT_HEADER, "msclip_ext_abi_version", "extension ABI"),
     ("_EXT2", "EXT2_ABI_VERSION", abi.EXT2_HEADER, "msclip_ext2_abi_version", "row-scale extension ABI"),
     ("_EXT3", "EXT3_ABI_VERSION", abi.EXT3_HEADER, "msclip_ext3_abi_version", "LAMB extension ABI"),
+    ("_EXT4", "EXT4_ABI_VERSION", abi.EXT4_HEADER, "msclip_ext4_abi_version", "non-finite guard extension ABI"),
 )
 EXPORTS, EXT_EXPORTS, EXT2_EXPORTS, EXT3_EXPORTS = (tuple(t.protos) for t in (_ABI, _EXT, _EXT2, _EXT3))
+EXT4_EXPORTS = tuple(_EXT4.protos)
 (GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor, SumsqTensor, AccumTensor) = (
     _ABI.structs[n] for n in (
         "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item",
@@ -1760,7 +1765,11 @@ class AdamwPlan:
     is derived from this one's (g, n) and set_grads writes both; one partial per 32 K-element chunk lands in `partials`, and
     `clip` holds {total_norm, coef} on the device.  `joined`: one bool per item, True where an item's tensors ALWAYS start
     where the previous item's end (the pieces of one parameter that differ in their packed copy): such a run is one entry
-    of the norm's table, so the norm is chunked over whole gradient tensors, as hip.grad_norm chunks them."""
+    of the norm's table, so the norm is chunked over whole gradient tensors, as hip.grad_norm chunks them.
+
+    The non-finite guard (run(..., guard=True), include/msclip_ext4.h): `guard_state`, a device int32[4] zeroed here once --
+    {this run's verdict, the count of skipped runs since construction, the smallest index of a non-finite partial or -1, the
+    number of non-finite partials}; `skip` is the 0-dim view of the verdict."""
 
     _item = AdamwTensor                                      # (LambPlan: the same members, then its own)
 
@@ -1799,6 +1808,8 @@ class AdamwPlan:
         self.partials = torch.empty(max(self.n_partials, 1), dtype=torch.float32, device=self.device) if n else None
         self.clip = torch.empty(2, dtype=torch.float32, device=self.device) if n else None
         self.norm, self.coef = (self.clip[0], self.clip[1]) if n else (None, None)      # 0-dim views, written by every clipped run
+        self.guard_state = torch.zeros(4, dtype=torch.int32, device=self.device) if n else None
+        self.skip = self.guard_state[0] if n else None        # 0-dim view, written by every guarded run
 
     def set_grads(self, ptrs):
         """Device addresses of this step's gradients, one per item (same element counts as at construction)."""
@@ -1812,27 +1823,41 @@ class AdamwPlan:
         for a, (lr, wd) in zip(self.arr, rates):
             a.lr, a.weight_decay = lr, wd
 
-    def run(self, beta1, beta2, eps, step, max_norm=None):
+    def run(self, beta1, beta2, eps, step, max_norm=None, guard=False):
         """max_norm None: one msclip_adamw_multi call.  Otherwise three calls on the current stream, nothing read back:
         msclip_grad_sumsq -> msclip_clip_coef (self.clip = {total_norm, coef}) -> msclip_adamw_multi_clipped, the update
-        of torch.nn.utils.clip_grad_norm_(params, max_norm) + AdamW with the gradients left as they are."""
+        of torch.nn.utils.clip_grad_norm_(params, max_norm) + AdamW with the gradients left as they are.
+        guard: always three calls, msclip_grad_sumsq -> msclip_clip_coef_guarded (self.clip, and the verdict in
+        self.guard_state) -> msclip_adamw_multi_guarded, which writes nothing where a partial is NaN or Inf; with max_norm
+        None the norm is taken all the same (self.norm) and the update is the unclipped one.  `step` is then the caller's
+        count of APPLIED updates."""
         if not self.n:
             return
         with torch.cuda.device(self.device):
             L, st = lib(), _stream()
-            coef = self._clip_coef(L, st, max_norm)
-            if coef is None:
+            coef = self._clip_coef(L, st, max_norm, guard)
+            if guard:
+                _check(L.msclip_adamw_multi_guarded(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.guard_state), st),
+                       "msclip_adamw_multi_guarded")
+            elif coef is None:
                 _check(L.msclip_adamw_multi(self.arr, self.n, beta1, beta2, eps, step, st), "msclip_adamw_multi")
             else:
                 _check(L.msclip_adamw_multi_clipped(self.arr, self.n, beta1, beta2, eps, step, coef, st), "msclip_adamw_multi_clipped")
 
-    def _clip_coef(self, L, st, max_norm):
+    def _clip_coef(self, L, st, max_norm, guard=False):
         """The clip prologue of run(): msclip_grad_sumsq -> msclip_clip_coef on stream `st`, -> the device address of coef; None,
-        and nothing issued, where max_norm is None."""
-        if max_norm is None:
+        and nothing issued, where max_norm is None.  guard: both calls always, the second one msclip_clip_coef_guarded (with
+        max_norm 0 where it is None, as hip.grad_norm asks for the norm alone: -> None then too)."""
+        if max_norm is None and not guard:
             return None
         _check(L.msclip_grad_sumsq(self.sq, self.n_sq, _p(self.partials), self.n_partials, st), "msclip_grad_sumsq")
-        _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
+        if guard:
+            _check(L.msclip_clip_coef_guarded(_p(self.partials), self.n_partials, 0.0 if max_norm is None else float(max_norm),
+                                              _p(self.clip), _p(self.guard_state), st), "msclip_clip_coef_guarded")
+            if max_norm is None:
+                return None
+        else:
+            _check(L.msclip_clip_coef(_p(self.partials), self.n_partials, float(max_norm), _p(self.clip), st), "msclip_clip_coef")
         return ctypes.c_void_p(self.clip.data_ptr() + 4)
 
 
@@ -1867,20 +1892,26 @@ class LambPlan(AdamwPlan):
         for a, (lr, wd) in zip(self.arr, rates):
             a.lr, a.weight_decay, a.adapt = lr, wd, int(self.always_adapt or wd != 0.0)
 
-    def run(self, beta1, beta2, eps, step, max_norm=None, trust_clip=False):
+    def run(self, beta1, beta2, eps, step, max_norm=None, trust_clip=False, guard=False):
         """[msclip_grad_sumsq -> msclip_clip_coef ->] msclip_lamb_partials -> msclip_lamb_ratios -> msclip_lamb_apply on the
         current stream, nothing read back.  Afterwards self.ratio / param_norm / update_norm ([n_params] views of `result`)
-        hold this step's values; with max_norm, self.norm / self.coef as after AdamwPlan.run."""
+        hold this step's values; with max_norm, self.norm / self.coef as after AdamwPlan.run.
+        guard: msclip_grad_sumsq -> msclip_clip_coef_guarded always (AdamwPlan.run), and msclip_lamb_apply_guarded as the last
+        call; on a skipped run the ratios and norms of `result` mean nothing."""
         if not self.n:
             return
         with torch.cuda.device(self.device):
             L, st = lib(), _stream()
-            coef = self._clip_coef(L, st, max_norm)
+            coef = self._clip_coef(L, st, max_norm, guard)
             _check(L.msclip_lamb_partials(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.lamb_partials),
                                           2 * self.n_chunks, st), "msclip_lamb_partials")
             _check(L.msclip_lamb_ratios(_p(self.lamb_partials), _p(self.first_chunk), self.n_params, self.n_chunks,
                                         int(bool(trust_clip)), _p(self.result), st), "msclip_lamb_ratios")
-            _check(L.msclip_lamb_apply(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.result), st), "msclip_lamb_apply")
+            if guard:
+                _check(L.msclip_lamb_apply_guarded(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.result),
+                                                   _p(self.guard_state), st), "msclip_lamb_apply_guarded")
+            else:
+                _check(L.msclip_lamb_apply(self.arr, self.n, beta1, beta2, eps, step, coef, _p(self.result), st), "msclip_lamb_apply")
 
 
 def adamw_multi(items, beta1, beta2, eps, step):

@@ -41,6 +41,7 @@ _LEAVES = ("attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "
 
 
 OPTIMIZERS = {"adamw": 1e-8, "lamb": 1e-6}              # TrainStep(optimizer=...): the default eps of each
+NONFINITE = (None, "skip", "raise")                     # TrainStep(nonfinite=...)
 
 
 class TrainStep:
@@ -48,7 +49,7 @@ class TrainStep:
 
     def __init__(self, model, lr=None, lr_share=None, wd=0.05, wd_share=None, betas=(0.9, 0.999), eps=None, bn="frozen",
                  without_wd=("bn", "bias", "ln"), clip_grad_norm=None, ema_decay=None, drop_path=None, drop_path_mode="sample",
-                 drop_path_seed=0, optimizer="adamw", trust_clip=False, always_adapt=False):
+                 drop_path_seed=0, optimizer="adamw", trust_clip=False, always_adapt=False, nonfinite=None):
         """bn = "frozen": BatchNorm with its running statistics (gamma / beta trained; the inference kernels' folded
         form); bn = "batch": train-mode BatchNorm -- per-GPU batch statistics in the forward, their backward, running
         statistics updated with momentum 0.1 (what the reference's modules do in train()).
@@ -73,8 +74,21 @@ class TrainStep:
         `optimizer`: "adamw" or "lamb" (TRAIN.OPTIMIZER, case-insensitive).  lamb is timm's Lamb: the AdamW update with each
         parameter tensor's rate scaled by its trust ratio ||w|| / ||u|| where its weight decay is not 0 (everywhere with
         `always_adapt`), capped at 1 with `trust_clip`; step() describes it.  `eps`: None takes the optimizer's default, 1e-8
-        for adamw (torch.optim.AdamW's), 1e-6 for lamb (timm's)."""
+        for adamw (torch.optim.AdamW's), 1e-6 for lamb (timm's).
+        `nonfinite`: None (default): a NaN or Inf in the gradients reaches the parameters, as it does in torch, and step() is
+        what it was before the option existed.  "skip" (TRAIN.SKIP_NONFINITE): step() leaves parameters, moments and the
+        engine's packed copies untouched when any gradient element is NaN or Inf -- decided on the device, nothing read back
+        in the step -- and the bias corrections count applied updates only (step() says how).  "raise"
+        (TRAIN.DETECT_ANOMALY): "skip", then step() reads the verdict and raises FloatingPointError naming the gradient
+        tensors; model and optimizer state are intact when it does."""
         assert bn in ("frozen", "batch")
+        if nonfinite not in NONFINITE:
+            raise ValueError(f"nonfinite = {nonfinite!r}: one of {NONFINITE}")
+        self.nonfinite = nonfinite
+        self.last_skipped = None
+        self._skip_base = 0                  # skipped steps counted by earlier optimizer tables / a resumed checkpoint
+        self._skip_seen = 0                  # ... and by the current table, as of the last verdict that arrived
+        self._skip_host = self._skip_event = None      # pinned int32 pair <- guard_state[0:2] of the last step(), its event
         optimizer = str(optimizer).lower()
         if optimizer not in OPTIMIZERS:
             raise NotImplementedError(f"optimizer = {optimizer!r}: one of {OPTIMIZERS}")
@@ -1071,6 +1085,9 @@ class TrainStep:
                 plan.set_rates([groups[k] for k, _ in plan.pieces])
                 plan.rates_for = (self.lr, self.lr_share, self.wd, self.wd_share)
             return plan
+        if self.nonfinite is not None:                   # a new table counts its skipped runs from 0: keep what the old one counted
+            self._skip_base = self._resolve_skips()
+            self._skip_seen = 0
         dests = self._packed_destinations() if pk_ok else {}
         items, pieces, names, hold = [], [], {}, []
         for k, p, lr, wd in self.param_groups():
@@ -1099,6 +1116,36 @@ class TrainStep:
         self._plan = plan
         return plan
 
+    # ------------------------------------------------------------------ non-finite guard
+    def _resolve_skips(self):
+        """-> the number of skipped steps so far.  Waits for the last guarded step()'s copy of the verdict (the one host wait
+        of the guard; a no-op where none is pending or it has arrived)."""
+        if self._skip_event is not None:
+            self._skip_event.synchronize()
+            self._skip_event = None
+            self._skip_seen = int(self._skip_host[1])
+        return self._skip_base + self._skip_seen
+
+    @property
+    def skipped_steps(self):
+        """step() calls that left the model untouched (host int; reading it waits for the last step()'s verdict).  0 without
+        the guard."""
+        return self._resolve_skips()
+
+    @property
+    def applied_steps(self):
+        """step() calls that updated the model: steps - skipped_steps."""
+        return self.steps - self._resolve_skips()
+
+    def nonfinite_gradients(self):
+        """Names of the parameters whose gradient of the LAST step() held a NaN or an Inf (more precisely: whose chunks of the
+        norm's table hold a non-finite partial sum of squares), in the table's order; [] where the step was clean.
+        Synchronises (reads the optimizer table's partials); valid until the next step()."""
+        plan = getattr(self, "_plan", None)
+        if self.nonfinite is None or plan is None or plan.partials is None:
+            raise RuntimeError("TrainStep.nonfinite_gradients() needs TrainStep(..., nonfinite=...) and a step() before it")
+        return nonfinite_names(plan.partials[:plan.n_partials].cpu(), list(plan.names.items()))
+
     @hip.off_default_stream
     def step(self, grads, world_average=False):
         """AdamW on the module's fp32 parameters (msclip_adamw_multi), which also writes the engine's bf16 copies of the
@@ -1114,7 +1161,8 @@ class TrainStep:
         whatever number of chunks accumulate() summed; every rank updates its own shadow from parameters that are identical
         across ranks: no collective) and self.ema_updates counts it.  Afterwards self.last_grad_norm / self.last_clip_coef are 0-dim device tensors, views of the optimizer
         table's block that are valid until the next step(); .item() on them is the caller's choice of when to synchronise
-        (step() never does).  A non-finite norm is not skipped: it reaches the parameters as it does in torch.
+        (step() never does).  Without the non-finite guard (below) a non-finite norm is not skipped: it reaches the parameters
+        as it does in torch.
         Ranks: the norm is taken after the rank averaging (backward()'s, or world_average=True's), so it is the norm of the
         averaged gradient, identical on every rank, with no further collective.  After accumulate() it is the norm of the SUM
         over the chunks, which is what a one-shot step on the whole batch clips.
@@ -1127,25 +1175,54 @@ class TrainStep:
         the clip norm, come from parameters and averaged gradients that are identical on every rank: no collective.
         Afterwards self.last_trust_ratio / last_param_norm / last_update_norm are {parameter name: 0-dim device view}, valid
         until the next step() and never read back here; last_trust_ratio holds r as computed, also for a tensor whose step
-        did not use it.  They are None under adamw."""
+        did not use it.  They are None under adamw.
+
+        nonfinite = "skip" / "raise" (include/msclip_ext4.h): the norm's two calls run always (msclip_grad_sumsq ->
+        msclip_clip_coef_guarded; last_grad_norm is set also without clipping, last_clip_coef stays None then) and leave a
+        verdict on the device; the update is msclip_adamw_multi_guarded / msclip_lamb_apply_guarded, which writes nothing where
+        any partial is NaN or Inf: parameters, moments and packed copies keep their bits.  The trust ratios of a skipped
+        step mean nothing; the EMA shadows take one more pull toward the unchanged parameters (what timm's loop does when a
+        GradScaler skips).  Forward-side state (BatchNorm running statistics under bn="batch", the stochastic-depth generator)
+        is not undone.  The step number handed to the library -- the bias corrections' exponent -- is the count of APPLIED
+        updates: after its launches step() queues a non-blocking copy of {verdict, skipped total} into pinned host memory and
+        records an event, without waiting; the NEXT step() waits for that event, i.e. for the previous step's optimizer phase,
+        and passes steps - skipped.  So with the guard on the host runs at most one step ahead of the device, and this is the
+        only case in which step() waits; self.steps keeps counting calls.  self.last_skipped is the verdict as a 0-dim device
+        int view (valid until the next step()), skipped_steps / applied_steps are host ints, nonfinite_gradients() names
+        the tensors.  "raise" reads this step's verdict (a synchronisation) and raises FloatingPointError after everything else
+        step() does.  Ranks: the verdict is taken on the averaged gradient, so it is identical on every rank with no collective
+        (not run on more than one rank).  After accumulate() it is the verdict on the sum over the chunks.  A run without
+        skips is bitwise the unguarded run."""
         if self.lr is None:
             raise ValueError("TrainStep.step() needs a learning rate: TrainStep(model, lr=...) or train.from_config(model, config)")
         self._ema_live("step")
         if hasattr(grads, "check_fresh"):
             grads.check_fresh()
+        guard = self.nonfinite is not None
+        skipped = self._resolve_skips() if guard else 0      # (before the count moves: the previous step's verdict is in)
         self.steps += 1
         max_norm = float(self.clip_grad_norm) if self.clip_grad_norm else None
         with torch.no_grad():
             if world_average:
                 world_average_(grads)
             plan = self._adamw_plan(grads)
-            plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm, **self._run_options)
+            if guard:
+                plan.run(self.betas[0], self.betas[1], self.eps, self.steps - skipped, max_norm, guard=True, **self._run_options)
+            else:
+                plan.run(self.betas[0], self.betas[1], self.eps, self.steps, max_norm, **self._run_options)
             plan.hold = None
             if self._ema is not None:                # behind the AdamW launch on the same stream: the shadows follow the new values
                 self._ema.plan.run(self.ema_decay)
                 self.ema_updates += 1
+            if guard and plan.n:                     # {verdict, skipped total of this table} -> pinned memory, read by the next step()
+                if self._skip_host is None:
+                    self._skip_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+                self._skip_host.copy_(plan.guard_state[:2], non_blocking=True)
+                self._skip_event = torch.cuda.Event()
+                self._skip_event.record()
+                self.last_skipped = plan.skip
         if max_norm is None:
-            self.last_grad_norm = self.last_clip_coef = None
+            self.last_grad_norm, self.last_clip_coef = (plan.norm if guard else None), None
         else:
             self.last_grad_norm, self.last_clip_coef = plan.norm, plan.coef
         if self.optimizer == "lamb":
@@ -1156,7 +1233,10 @@ class TrainStep:
             self.eng.repack_after_optimizer()
         else:
             self.eng.refresh(force=True)
-
+        if self.nonfinite == "raise" and plan.n and int(plan.skip.item()):
+            names = self.nonfinite_gradients()
+            raise FloatingPointError(f"TrainStep.step(): step {self.steps} was skipped, NaN or Inf in the gradient of {names} "
+                                     f"({len(names)} of {len(plan.names)} tensors); parameters and optimizer state are untouched")
 
     # ------------------------------------------------------------------ weight EMA
     def _ema_live(self, what):
@@ -1348,21 +1428,24 @@ def _optimizer_state_dict(ts):
     'optimizer' (lib/utils/utils.py:177-183)."""
     groups, index = {}, {}
     state = {}
+    guard = getattr(ts, "nonfinite", None) is not None      # with the guard: 'step' is the applied count, 'msclip' says how many were skipped
+    skipped = int(ts.skipped_steps) if guard else 0
+    extra = {"skipped_steps": skipped} if guard else {}
     for i, (k, p, lr, wd) in enumerate(ts.param_groups()):
         index[k] = i
         groups.setdefault((lr, wd), []).append(i)
         st = ts.state.get(k)
         if st is not None:
-            state[i] = {"step": torch.tensor(float(ts.steps)), "exp_avg": st[0].detach().cpu(), "exp_avg_sq": st[1].detach().cpu()}
+            state[i] = {"step": torch.tensor(float(ts.steps - skipped)), "exp_avg": st[0].detach().cpu(), "exp_avg_sq": st[1].detach().cpu()}
     if getattr(ts, "optimizer", "adamw") == "lamb":       # timm Lamb's group keys; the adamW dict is what it was before lamb existed
         pgs = [{"lr": lr, "weight_decay": wd, "bias_correction": True, "betas": tuple(ts.betas), "eps": ts.eps, "grad_averaging": True,
                 "max_grad_norm": float(ts.clip_grad_norm) if ts.clip_grad_norm else None, "trust_clip": ts.trust_clip,
                 "always_adapt": ts.always_adapt, "params": idx} for (lr, wd), idx in groups.items()]
         return {"state": state, "param_groups": pgs,
-                "msclip": {"steps": ts.steps, "bn": ts.bn, "names": list(index), "optimizer": "lamb"}}
+                "msclip": dict({"steps": ts.steps, "bn": ts.bn, "names": list(index), "optimizer": "lamb"}, **extra)}
     pgs = [{"lr": lr, "weight_decay": wd, "betas": tuple(ts.betas), "eps": ts.eps, "amsgrad": False, "params": idx}
            for (lr, wd), idx in groups.items()]
-    return {"state": state, "param_groups": pgs, "msclip": {"steps": ts.steps, "bn": ts.bn, "names": list(index)}}
+    return {"state": state, "param_groups": pgs, "msclip": dict({"steps": ts.steps, "bn": ts.bn, "names": list(index)}, **extra)}
 
 
 def _check_optimizer_kind(opt, ts, path):
@@ -1416,6 +1499,11 @@ def resume_checkpoint(model, ts, path):
         p = params[names[int(i)]]
         ts.state[names[int(i)]] = (st["exp_avg"].to(p.device).contiguous(), st["exp_avg_sq"].to(p.device).contiguous())
     ts.steps = int(opt["msclip"]["steps"])
+    skipped = int(opt["msclip"].get("skipped_steps", 0))  # written with the non-finite guard on
+    if getattr(ts, "nonfinite", None) is not None:        # both counters; a verdict still in flight belongs to the replaced state
+        ts._skip_base, ts._skip_seen, ts._skip_event, ts.last_skipped = skipped, 0, None, None
+    else:
+        ts.steps -= skipped                               # no guard here: the step count IS the bias corrections' exponent
     if ts.ema_shadow is not None:
         ts._ema.load(obj["ema_shadow_states"])
     if ts._dp_gen is not None:
@@ -1436,11 +1524,12 @@ def from_config(model, config, bn="batch", drop_path_mode="sample"):
     CUSTOM.LR_SHARE / WD_SHARE for the modality-shared tensors (already scaled with the world size by update_config,
     lib/config/default.py:299-304), TRAIN.CLIP_GRAD_NORM (global-norm clipping inside step(); 0.0 = off), TRAIN.EMA_DECAY
     (shadow weights updated inside step(); absent or 0.0 = off), MODEL.SPEC.VISION.DROP_PATH (stochastic depth on the vision
-    blocks, one draw per image per branch unless drop_path_mode says "position"; absent or 0.0 = off).
+    blocks, one draw per image per branch unless drop_path_mode says "position"; absent or 0.0 = off), TRAIN.DETECT_ANOMALY /
+    TRAIN.SKIP_NONFINITE (nonfinite_setting: the non-finite guard of step(); both absent or False = off).
     bn = "batch" (default): train-mode BatchNorm as the reference's modules run in train(); "frozen": running statistics."""
     settings = optimizer_settings(config)
     ts = TrainStep(model, bn=bn, ema_decay=ema_setting(config), drop_path=drop_path_setting(config), drop_path_mode=drop_path_mode,
-                   **settings)
+                   nonfinite=nonfinite_setting(config), **settings)
     if "clip_grad_norm" not in settings:             # (lamb: already settled between CLIP_GRAD_NORM and OPTIMIZER_ARGS.max_grad_norm)
         ts.clip_grad_norm = float(config.TRAIN.get("CLIP_GRAD_NORM", 0.0) or 0.0)      # 0.0: off (lib/config/default.py:153)
     ts.schedule = lr_schedule(config)            # TRAIN.LR_SCHEDULER of the yaml (None when the config has none)
@@ -1497,6 +1586,34 @@ def ema_setting(config):
     """TRAIN.EMA_DECAY of a reference config as TrainStep's `ema_decay` (needs no GPU): None when the key is absent or 0.0,
     the reference's default (lib/config/default.py:146; its run name carries 'ema<decay>' only when > 0, :268-270)."""
     return float(config.TRAIN.get("EMA_DECAY", 0.0) or 0.0) or None
+
+
+def nonfinite_setting(config):
+    """TrainStep's `nonfinite` from a reference config (needs no GPU): TRAIN.DETECT_ANOMALY True (lib/config/default.py:151; the
+    unreleased trainer's switch for torch's anomaly detection) -> "raise"; else TRAIN.SKIP_NONFINITE True (this
+    project's key) -> "skip"; else None."""
+    if bool(config.TRAIN.get("DETECT_ANOMALY", False)):
+        return "raise"
+    return "skip" if bool(config.TRAIN.get("SKIP_NONFINITE", False)) else None
+
+
+def nonfinite_names(partials, names_and_sizes):
+    """The chunk -> parameter map of the norm's table as a pure function (CPU tensors are fine).  partials: the fp32 partial sums
+    of squares of msclip_grad_sumsq, one per started 32 K-element chunk; names_and_sizes: [(parameter name, element count)] in
+    the table's order, one entry per Parameter object (the joined pieces of in_proj are one entry).  -> the names whose chunks
+    hold a NaN or an Inf, in that order."""
+    chunk = hip.CLIP_CHUNK
+    total = sum((n + chunk - 1) // chunk for _, n in names_and_sizes)
+    if partials.dim() != 1 or partials.numel() != total:
+        raise ValueError(f"partials: {tuple(partials.shape)}, the table has {total} chunks")
+    bad = ~torch.isfinite(partials)
+    out, c = [], 0
+    for name, n in names_and_sizes:
+        k = (n + chunk - 1) // chunk
+        if k and bool(bad[c:c + k].any()):
+            out.append(name)
+        c += k
+    return out
 
 
 def drop_path_setting(config):

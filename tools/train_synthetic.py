@@ -2,7 +2,7 @@
 
     python tools/train_synthetic.py --model b32-yfcc-msclips --batch 64 --steps 20 [--bn batch|frozen] [--lr 2e-5]
                                     [--accumulate K] [--clip-grad-norm X] [--ema-decay D] [--drop-path P [--drop-path-mode M]]
-                                    [--optimizer adamw|lamb [--trust-clip]]
+                                    [--optimizer adamw|lamb [--trust-clip]] [--nonfinite skip|raise]
 
 --accumulate K: every optimizer step is ONE contrastive batch of K x --batch pairs, taken chunk by chunk through
 TrainStep.accumulate (exact: every pair competes with all K x batch - 1 others); the loss printed is that batch's.
@@ -20,6 +20,10 @@ training losses then carry the masks' noise; the inference-path loss at the end 
 --optimizer lamb: TRAIN.OPTIMIZER lamb, every parameter tensor's rate scaled by its trust ratio ||w|| / ||u|| inside step() (on
 the device; --trust-clip caps the ratio at 1); every fifth step also prints the smallest and largest ratio of the tensors that
 adapt.  LAMB's rates are larger than AdamW's: try --lr 2e-3.
+
+--nonfinite skip|raise: TRAIN.SKIP_NONFINITE / TRAIN.DETECT_ANOMALY, a step whose gradient holds a NaN or an Inf leaves the model
+and the optimizer state untouched (decided on the device; raise: step() then raises FloatingPointError naming the tensors); the
+count of skipped steps is printed at the end.
 
 Prints the contrastive loss of every step (the same fixed batches are cycled, so it has to fall), the step time and,
 at the end, the inference-path loss of the first batch with the trained weights / running statistics.  One process per
@@ -58,6 +62,8 @@ def main():
                     help="one draw per image (sample) or per token position, shared by the batch (position: the reference module's layout)")
     ap.add_argument("--optimizer", choices=("adamw", "lamb"), default="adamw", help="TRAIN.OPTIMIZER (lamb: per-tensor trust ratios)")
     ap.add_argument("--trust-clip", action="store_true", help="lamb: cap the trust ratio at 1 (OPTIMIZER_ARGS.trust_clip)")
+    ap.add_argument("--nonfinite", choices=("skip", "raise"), default=None,
+                    help="skip the optimizer step on NaN / Inf gradients (TRAIN.SKIP_NONFINITE), or skip and raise (TRAIN.DETECT_ANOMALY)")
     args = ap.parse_args()
     from msclip_amd import comm as C, synth, train
     from msclip_amd.clip_openai_pe_res_v1 import get_clip_model
@@ -73,7 +79,8 @@ def main():
         hip.use_compute_stream(dev)
     cfg = named_config(args.model, ["TRAIN.CLIP_GRAD_NORM", str(args.clip_grad_norm), "TRAIN.EMA_DECAY", str(args.ema_decay),
                                     "MODEL.SPEC.VISION.DROP_PATH", str(args.drop_path)]
-                       + (["TRAIN.OPTIMIZER", "lamb", "TRAIN.OPTIMIZER_ARGS.trust_clip", str(args.trust_clip)] if args.optimizer == "lamb" else []))
+                       + (["TRAIN.OPTIMIZER", "lamb", "TRAIN.OPTIMIZER_ARGS.trust_clip", str(args.trust_clip)] if args.optimizer == "lamb" else [])
+                       + ({"skip": ["TRAIN.SKIP_NONFINITE", "True"], "raise": ["TRAIN.DETECT_ANOMALY", "True"]}.get(args.nonfinite, [])))
     from bench import load_schema
     model = get_clip_model(cfg)
     model.load_state_dict(synth.synth_state_dict(load_schema(args.model), seed=0), strict=True)
@@ -106,7 +113,7 @@ def main():
         ms = 1e3 * (time.perf_counter() - t0)
         note = ""
         if ts.last_grad_norm is not None and step % 5 == 0:   # one more read on a step that has just read the loss
-            note = f"  grad norm {ts.last_grad_norm.item():.4g} (clipped to {ts.clip_grad_norm:g})"
+            note = f"  grad norm {ts.last_grad_norm.item():.4g}" + (f" (clipped to {ts.clip_grad_norm:g})" if ts.clip_grad_norm else "")
         if ts.last_trust_ratio is not None and step % 5 == 0:
             adapting = torch.stack([ts.last_trust_ratio[k] for k, _, _, wd in ts.param_groups() if wd != 0.0 or ts.always_adapt])
             note += f"  trust ratio {adapting.min().item():.3g} .. {adapting.max().item():.3g}"
@@ -124,6 +131,8 @@ def main():
     if rank == 0:
         print(f"first {'chunk' if K > 0 else 'batch'} through the inference path (running statistics): loss {inf:.4f}"
               + (f", under the EMA weights (decay {ts.ema_decay:g}, {ts.ema_updates} updates) {ema_inf:.4f}" if ema_inf is not None else ""))
+        if ts.nonfinite is not None:
+            print(f"non-finite guard ({ts.nonfinite}): {ts.skipped_steps} of {ts.steps} steps skipped")
         print("OK" if ok else "FAILED: the loss did not fall")
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
