@@ -1,5 +1,5 @@
 """The C ABI as Python binds it, read from include/msclip_hip.h: the header is the only statement of it.  The extension headers
-include/msclip_ext.h, msclip_ext2.h, msclip_ext3.h and msclip_ext4.h (declarations newer than that header's ABI version) are read by the same
+include/msclip_ext.h, msclip_ext2.h, msclip_ext3.h, msclip_ext4.h and msclip_ext5.h (declarations newer than that header's ABI version) are read by the same
 rules, each under its own version macro.
 
 The mapping rule, for prototype parameters and struct members alike:
@@ -33,6 +33,10 @@ EXT3_VERSION_MACRO = "MSCLIP_EXT3_ABI_VERSION"
 # msclip_hip.h and to msclip_lamb_tensor of the third, so it is read with both headers' names known
 EXT4_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext4.h")
 EXT4_VERSION_MACRO = "MSCLIP_EXT4_ABI_VERSION"
+# the fifth extension header (linear probing: the classifier's row pass, its loss fold, the bf16 hi/lo split): scalars and plain
+# pointers only, read like the first
+EXT5_HEADER = os.path.join(os.path.dirname(HEADER), "msclip_ext5.h")
+EXT5_VERSION_MACRO = "MSCLIP_EXT5_ABI_VERSION"
 
 Abi = collections.namedtuple("Abi", "version structs protos")   # int, {C name: Structure subclass}, {name: (restype, [argtypes])}
 

@@ -19,8 +19,8 @@ LIB_PATH = os.environ.get("MSCLIP_HIP_LIB") or os.path.join(_HERE, "csrc", "libm
 INT_MAX = 2 ** 31 - 1
 # The headers, each read once.  include/msclip_hip.h is the statement of the C ABI; the extension headers hold the declarations
 # newer than ABI_VERSION, each a table of its own, so that _ABI / EXPORTS / ABI_VERSION keep describing msclip_hip.h alone: the
-# weight EMA, the row-scale entry points (stochastic depth), LAMB and the non-finite guard, the last three pointing to structs of
-# msclip_hip.h (the guard also to LAMB's).
+# weight EMA, the row-scale entry points (stochastic depth), LAMB, the non-finite guard and linear probing, the middle three
+# pointing to structs of msclip_hip.h (the guard also to LAMB's).
 _ABI = abi.load()
 _EXT = abi.load(abi.EXT_HEADER, abi.EXT_VERSION_MACRO)
 _EXT2 = abi.load(abi.EXT2_HEADER, abi.EXT2_VERSION_MACRO, known=tuple(_ABI.structs))
@@ -28,6 +28,8 @@ _EXT3 = abi.load(abi.EXT3_HEADER, abi.EXT3_VERSION_MACRO, known=tuple(_ABI.struc
 _EXT4 = abi.load(abi.EXT4_HEADER, abi.EXT4_VERSION_MACRO, known=tuple(_ABI.structs) + tuple(_EXT3.structs))
 ABI_VERSION, EXT_ABI_VERSION, EXT2_ABI_VERSION, EXT3_ABI_VERSION = (t.version for t in (_ABI, _EXT, _EXT2, _EXT3))
 EXT4_ABI_VERSION = _EXT4.version
+_EXT5 = abi.load(abi.EXT5_HEADER, abi.EXT5_VERSION_MACRO)             # linear probing (linear_probe.py)
+EXT5_ABI_VERSION = _EXT5.version
 # What lib() binds and verifies, one row per header: (attribute of the table above, attribute of its version, header, the
 # library's version function, what a refusal calls the version).  By attribute name: lib() takes both as they are when it runs.
 _BOUND = (
@@ -36,9 +38,11 @@ _BOUND = (
     ("_EXT2", "EXT2_ABI_VERSION", abi.EXT2_HEADER, "msclip_ext2_abi_version", "row-scale extension ABI"),
     ("_EXT3", "EXT3_ABI_VERSION", abi.EXT3_HEADER, "msclip_ext3_abi_version", "LAMB extension ABI"),
     ("_EXT4", "EXT4_ABI_VERSION", abi.EXT4_HEADER, "msclip_ext4_abi_version", "non-finite guard extension ABI"),
+    ("_EXT5", "EXT5_ABI_VERSION", abi.EXT5_HEADER, "msclip_ext5_abi_version", "linear-probe extension ABI"),
 )
 EXPORTS, EXT_EXPORTS, EXT2_EXPORTS, EXT3_EXPORTS = (tuple(t.protos) for t in (_ABI, _EXT, _EXT2, _EXT3))
 EXT4_EXPORTS = tuple(_EXT4.protos)
+EXT5_EXPORTS = tuple(_EXT5.protos)
 (GemmDesc, QkvAttnDesc, BnBwdSide, FoldItem, PackItem, TransposeItem, AdamwTensor, SumsqTensor, AccumTensor) = (
     _ABI.structs[n] for n in (
         "msclip_gemm_desc", "msclip_qkvattn_desc", "msclip_bn_bwd_side", "msclip_fold_item", "msclip_pack_item",
@@ -2026,3 +2030,56 @@ class EmaPlan:
 def ema_update(shadows, params, decay):
     """One msclip_ema_multi call over lists of fp32 tensors (see EmaPlan)."""
     EmaPlan(shadows, params).run(decay)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# linear probing (include/msclip_ext5.h, csrc/probe.hip; the driver is linear_probe.py)
+# ---------------------------------------------------------------------------------------------------------------------
+PROBE_ROWS = 32                                          # MSCLIP_PROBE_ROWS: rows of a workgroup of msclip_probe_ce_rows
+
+
+def split_bf16(x, out=None):
+    """fp32 [M, C] -> bf16 [M, 2 C] = (hi | lo), hi = bf16(x), lo = bf16(x - float(hi)), in one pass (msclip_split_bf16).  `out`:
+    a bf16 matrix (a column window of a wider one is fine) whose first 2 C columns are written."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 2 and x.stride(1) == 1
+    M, C = x.shape
+    if out is None:
+        out = torch.empty(M, 2 * C, dtype=torch.bfloat16, device=x.device)
+    _bf16(out)
+    assert out.shape[0] == M and out.shape[1] >= 2 * C
+    _check(lib().msclip_split_bf16(_p(x), x.stride(0), _p(out), out.stride(0), M, C, _stream()), "msclip_split_bf16")
+    return out
+
+
+def probe_ce_rows(S, bias, labels, C, w, *, lse=None, G_hi=None, G_lo=None, loss_part=None, colsum_part=None, pred=None, rank=None,
+                  bad_part=None):
+    """msclip_probe_ce_rows over the fp32 logits block S [R, >= Cpad] (include/msclip_ext5.h states the outputs): Cpad is G_hi's
+    width, or S's without G.  Partials: one entry / row per (R + 31) // 32 workgroups."""
+    assert S.dtype == torch.float32 and S.is_cuda and S.dim() == 2 and S.stride(1) == 1
+    R = S.shape[0]
+    Cpad = G_hi.shape[1] if G_hi is not None else S.shape[1]
+    nwg = (R + PROBE_ROWS - 1) // PROBE_ROWS
+    for t, dt in ((bias, torch.float32), (lse, torch.float32), (labels, torch.int32), (pred, torch.int32), (rank, torch.int32),
+                  (bad_part, torch.int32), (loss_part, torch.float64), (colsum_part, torch.float32)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.stride(-1) == 1), dt
+    assert bias is None or bias.numel() >= C
+    for t in (labels, lse, pred, rank):
+        assert t is None or t.numel() >= R
+    for t in (loss_part, bad_part):
+        assert t is None or t.numel() >= nwg
+    ldg = ldp = 0
+    if G_hi is not None:
+        _bf16(G_hi), _bf16(G_lo)
+        assert G_hi.shape == G_lo.shape and G_hi.shape[0] >= R and G_hi.stride(0) == G_lo.stride(0)
+        assert colsum_part is not None and colsum_part.dim() == 2 and colsum_part.shape[0] >= nwg and colsum_part.shape[1] >= Cpad
+        ldg, ldp = G_hi.stride(0), colsum_part.stride(0)
+    _check(lib().msclip_probe_ce_rows(_p(S), S.stride(0), _p(bias), _p(labels), R, C, Cpad, w, _p(lse), _p(G_hi), _p(G_lo), ldg,
+                                      _p(loss_part), _p(colsum_part), ldp, _p(pred), _p(rank), _p(bad_part), _stream()),
+           "msclip_probe_ce_rows")
+
+
+def probe_loss_fold(loss_part, n, denom, out):
+    """out[0] (float64) = sum(loss_part[:n]) / denom, folded in double in a fixed order (msclip_probe_loss_fold)."""
+    assert loss_part.dtype == torch.float64 and out.dtype == torch.float64 and loss_part.is_cuda and out.is_cuda
+    assert loss_part.numel() >= n and loss_part.is_contiguous()
+    _check(lib().msclip_probe_loss_fold(_p(loss_part), n, denom, _p(out), _stream()), "msclip_probe_loss_fold")
