@@ -132,14 +132,10 @@ def gather_rows_async(t, out=None):
         out = torch.empty(shape, dtype=t.dtype, device=t.device)
     if not t.is_cuda:
         return out, GatherHandle(dist.all_gather_into_tensor(out, t, async_op=True), out, None)
+    from .hip import forked
     side = side_stream(t.device)
-    ready = torch.cuda.Event()
-    ready.record(torch.cuda.current_stream(t.device))
-    side.wait_event(ready)
-    with torch.cuda.stream(side):
+    with forked(side, out, t):
         work = dist.all_gather_into_tensor(out, t, async_op=True)
-    out.record_stream(side)
-    t.record_stream(side)
     return out, GatherHandle(work, out, side)
 
 
@@ -255,18 +251,14 @@ class GradReducer:
             # wgrad lane stream (gradgemm.wgrad_async): the compute stream itself waits for neither and goes on with the
             # backward pass
             from .gradgemm import lane_stream
+            from .hip import forked
             side = side_stream(dev)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-            side.wait_event(ready)
-            lane = lane_stream(dev)
-            if lane is not None:
-                side.wait_stream(lane)
-            with torch.cuda.stream(side):
+            with forked(side, *[g for _, g in copies]):
+                lane = lane_stream(dev)
+                if lane is not None:
+                    side.wait_stream(lane)
                 pack()
                 work = dist.all_reduce(payload, async_op=True)
-            for _, g in copies:
-                g.record_stream(side)
         else:
             pack()
             work = dist.all_reduce(payload, async_op=True)

@@ -130,7 +130,6 @@ class Engine:
         self.last_plan = None
         self._fp8_saved = {}            # calibrated hidden scales, restored into the fresh _BlockW objects of a re-pack
         self._fp8_warned = False
-        self.force_unfused = False      # the training step runs the conv side layer by layer: every map stays in the workspace
         with torch.cuda.device(self.dev), torch.no_grad():
             self._pack(model)
         self._stamp = self._fingerprint()
@@ -496,16 +495,18 @@ class Engine:
         if taps is not None:
             taps[name] = t[:n * L].view(n, L, -1).float().clone()                            # batch-first [B, L, C]
 
-    def _vision_front(self, img, w, Bi, taps=None, keep_pre=None, convs_done=False):
+    def _vision_front(self, img, w, Bi, taps=None, keep_pre=None, convs_done=False, unfused=False):
         """Stem + tokenisation (M.py:2416-2426) and stage 0 of the parallel branch (M.py:2436).  convs_done: the stem's maps
-        are already in the workspace (the training step's train-mode BatchNorm chain), only the tokenisation runs."""
+        are already in the workspace (the training step's train-mode BatchNorm chain), only the tokenisation runs.  unfused (here, in
+        _parallel_stage and _conv_branch_on_side_stream): the conv side layer by layer, as EngineOptions.front_unfused -- the
+        training step asks for it per call, so that every map its backward reads is in the workspace."""
         if self.patch:                                       # M.py:2657: conv1 as patchify + one dense GEMM (scatter + positional add fused)
             hip.patchify(img, w["PATCH"], Bi, self.S, self.S // self.g, self.patch_k)
             return self._tokenise(w["PATCH"], w, Bi, taps, keep_pre, weight=self.w_patch)
         if convs_done:
             return self._tokenise(w["stem"][-1], w, Bi, taps, keep_pre)
         first = self.stem_specs[0]
-        fused = (self.dual_w.shape[1] == 96 and self._fusable_3x3s2(first) and not (self.opt.front_unfused or self.force_unfused)
+        fused = (self.dual_w.shape[1] == 96 and self._fusable_3x3s2(first) and not (self.opt.front_unfused or unfused)
                  and img.numel() * img.element_size() < 2 ** 31
                  and Bi * self.h1 * self.h1 * (self.D // 16) * 2 < 2 ** 31)      # the kernel's own 32-bit offset limits
         if fused:
@@ -543,14 +544,14 @@ class Engine:
         hip.layernorm(xv, self.ln_pre.g, self.ln_pre.b, xv, w["Mv"])
         self._tap_tokens(taps, "tokens_ln_pre", xv, Bi, self.Lv)
 
-    def _parallel_stage(self, j, w, Bi):
+    def _parallel_stage(self, j, w, Bi, unfused=False):
         if j == 0:
             return
         c1, c2, cr, c3 = self.par_specs[j]
         t1, t2, tr = w["par_tmp"][j]
         src = w["par"][j - 1]
         lead = ((c1.kh, c1.kw, c1.stride, c1.pad, c1.cin, c1.cout) == (1, 1, 1, 0, 48, 48) and self._fusable_3x3s2(c2)
-                and not (self.opt.front_unfused or self.force_unfused) and src.numel() * 2 < 2 ** 31)
+                and not (self.opt.front_unfused or unfused) and src.numel() * 2 < 2 ** 31)
         if (lead and c2.cout == 48 and (cr.kh, cr.kw, cr.stride, cr.pad, cr.cin, cr.cout) == (1, 1, 2, 0, 48, 96)
                 and (c3.kh, c3.kw, c3.stride, c3.pad, c3.cin, c3.cout) == (1, 1, 1, 0, 48, 96)
                 and (cr.h_out, cr.w_out) == (c2.h_out, c2.w_out) and not self.opt.block_unfused):
@@ -589,7 +590,7 @@ class Engine:
         hip.adapter_combine_ln(w["X"][:w["Mv"]], t, a["dww"], a["dwb"], a["ln"].g, a["ln"].b, w["XA"], Bi,
                                self.Lv, self.g, self.usecls)
 
-    def _conv_branch_on_side_stream(self, w, Bi):
+    def _conv_branch_on_side_stream(self, w, Bi, unfused=False):
         """The parallel convolutional branch and the adapters' top-down halves depend on the image only (M.py:2436,
         2128-2159), not on the token stream: issue all of them on a side HIP stream right after the front pass and let
         each adapter wait for its own event.  They are HBM-bound, small-LDS kernels; the dispatcher places their
@@ -607,7 +608,7 @@ class Engine:
         events = []
         with torch.cuda.stream(side):
             for j in range(len(self.adapters)):
-                self._parallel_stage(j, w, Bi)
+                self._parallel_stage(j, w, Bi, unfused)
                 self._adapter_top(j, w, Bi, w["Ts"][j])
                 events.append(self._record(side))
         return events
@@ -1261,20 +1262,25 @@ class Engine:
                 if tb is not None:
                     self._tap_text(taps, f"tblock{i}", X[Mv:M], w, Bt)
 
-    def _head_image(self, w, Bi, norm=True, compact=False):               # M.py:2685-2690, 2983
+    def _head_image(self, w, Bi, norm=True, compact=False, x=None):       # M.py:2685-2690, 2983
+        """x: the residual matrix to read instead of the workspace's own XC (compact) / X (the training forward's)."""
+        if x is None:
+            x = w["XC"] if compact else w["X"]
         if compact:                                                       # cls rows already sit in XC[:Bi] (_last_block_tail)
-            hip.layernorm(w["XC"], self.ln_post.g, self.ln_post.b, w["hv"], Bi)
+            hip.layernorm(x, self.ln_post.g, self.ln_post.b, w["hv"], Bi)
         else:
-            hip.layernorm(w["X"], self.ln_post.g, self.ln_post.b, w["hv"], Bi, row_mul=self.Lv)
+            hip.layernorm(x, self.ln_post.g, self.ln_post.b, w["hv"], Bi, row_mul=self.Lv)
         hip.gemm(w["hv"], self.w_vproj, w["fv_raw"])
         if norm:
             hip.l2norm(w["fv_raw"], w["fv"], w["fvb"])
 
-    def _head_text(self, w, Bt, norm=True, compact=False, Bi=0):          # M.py:3057-3077
+    def _head_text(self, w, Bt, norm=True, compact=False, Bi=0, x=None):  # M.py:3057-3077
+        if x is None:
+            x = w["XC"] if compact else w["X"]
         if compact:                                                       # EOT rows already sit in XC[Bi:]
-            hip.layernorm(w["XC"][Bi:], self.ln_final.g, self.ln_final.b, w["ht"], Bt)
+            hip.layernorm(x[Bi:], self.ln_final.g, self.ln_final.b, w["ht"], Bt)
         else:
-            hip.layernorm(w["X"], self.ln_final.g, self.ln_final.b, w["ht"], Bt, row_idx=w["eot"])
+            hip.layernorm(x, self.ln_final.g, self.ln_final.b, w["ht"], Bt, row_idx=w["eot"])
         hip.gemm(w["ht"], self.w_tproj, w["ft_raw"])
         if norm:
             hip.l2norm(w["ft_raw"], w["ft"], w["ftb"])

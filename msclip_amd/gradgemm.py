@@ -93,29 +93,19 @@ def _ranks_share_a_gpu():
     return dist.is_available() and dist.is_initialized() and dist.get_backend() == "gloo"
 
 
+def lane_enabled():
+    """False: the lane's work runs on the calling stream instead (the A/B knob of options.TRAIN, or ranks that share a GPU)."""
+    return not (options.TRAIN.wgrad_sync or _ranks_share_a_gpu())
+
+
 def wgrad_async(dy_bf, x_bf, M, post=None, out=None):
     """wgrad(dy_bf, x_bf, M) on the lane stream.  The operands must not be overwritten in place afterwards (their memory
     may be freed: the caching allocator is told about the lane's use); the result may only be touched after join().
-    x_bf may be a callable that builds the operand: it runs on the lane as well."""
-    dev = dy_bf.device
-    if options.TRAIN.wgrad_sync or _ranks_share_a_gpu():
-        out = wgrad(dy_bf, x_bf() if callable(x_bf) else x_bf, M, out)    # everything on the calling stream (A/B knob; gloo test setups)
-        return post(out) if post is not None else out
-    cur, ln = torch.cuda.current_stream(dev), lane(dev)
-    ready = torch.cuda.Event()
-    ready.record(cur)
-    ln.wait_event(ready)
-    with torch.cuda.stream(ln):
-        if callable(x_bf):                               # the operand itself is lane work (a convolution's column matrix)
-            x_bf = x_bf()
-        else:
-            x_bf.record_stream(ln)
-        out = wgrad(dy_bf, x_bf, M, out)
-        if post is not None:
-            out = post(out)
-    dy_bf.record_stream(ln)
-    out.record_stream(cur)
-    return out
+    x_bf may be a callable that builds the operand: it runs on the lane as well (a convolution's column matrix)."""
+    def job():
+        dw = wgrad(dy_bf, x_bf() if callable(x_bf) else x_bf, M, out)
+        return post(dw) if post is not None else dw
+    return on_lane(job, dy_bf, *(() if callable(x_bf) else (x_bf,)))
 
 
 class WgradJob:
@@ -138,28 +128,21 @@ class WgradJob:
         tiles = ((self.N + 255) // 256) * ((self.K + 255) // 256)
         self.S = S = max(1, min(256 // tiles, M // 2048))
         Mpad = (M + 64 * S - 1) // (64 * S) * (64 * S)
-        dev = dy_bf.device
-        self.sync = options.TRAIN.wgrad_sync or _ranks_share_a_gpu()
         self.tn = _tn_ok(dy_bf, x_bf)
         if self.tn:
             # round 4: the split-K GEMM reads both operands token-major (LDS transpose reads): nothing to do until finish().
             # The operands stay referenced here (same contract as before: never overwritten in place afterwards).
             self.a, self.b, self.done = dy_bf, x_bf, None
             return
-        if self.sync:
+        if not lane_enabled():
             self.a, self.b, self.done = hip.transpose_bf16(dy_bf, M, Mpad), hip.transpose_bf16(x_bf, M, Mpad), None
             return
-        cur, ln = torch.cuda.current_stream(dev), lane(dev)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        ln.wait_event(ready)
-        with torch.cuda.stream(ln):
+        ln = lane(dy_bf.device)
+        with hip.forked(ln, dy_bf, x_bf):
             self.a = hip.transpose_bf16(dy_bf, M, Mpad)
             self.b = hip.transpose_bf16(x_bf, M, Mpad)
             self.done = torch.cuda.Event()
             self.done.record(ln)
-        dy_bf.record_stream(ln)
-        x_bf.record_stream(ln)
 
     def finish(self, out=None):
         """-> fp32 [N, K] (written into `out` when given, e.g. a gradient bucket's slot) on the calling stream."""
@@ -184,17 +167,10 @@ class WgradJob:
 def on_lane(fn, *operands):
     """fn() on the lane stream behind an event (same contract as wgrad_async: operands read-only afterwards, result valid
     after join).  For the other HBM-bound by-products of the backward that nothing on the critical path reads (bias sums)."""
-    dev = operands[0].device
-    if options.TRAIN.wgrad_sync or _ranks_share_a_gpu():
-        return fn()
-    cur, ln = torch.cuda.current_stream(dev), lane(dev)
-    ready = torch.cuda.Event()
-    ready.record(cur)
-    ln.wait_event(ready)
-    with torch.cuda.stream(ln):
+    if not lane_enabled():
+        return fn()                                      # everything on the calling stream
+    with hip.forked(lane(operands[0].device), *operands) as cur:
         out = fn()
-    for t in operands:
-        t.record_stream(ln)
     out.record_stream(cur)
     return out
 

@@ -233,6 +233,35 @@ def compute_stream(device):
     return cs
 
 
+class forked:
+    """`with hip.forked(side, *reads) as cur:` -- hand work to the stream `side` behind everything queued so far on the current
+    stream.  Entry: an event recorded on the current stream, `side` waits for it and becomes the current stream; `cur` is the
+    stream that was current (for result.record_stream(cur), or to record the body's own events on `side`).  Exit: the previous
+    stream is current again and the caching allocator is told that `side` reads every tensor of `reads` (memory the caller may
+    free before `side` has run).  Nothing joins: the caller orders its stream behind `side` with its own event or wait_stream.
+    A plain class, not a generator: ONE torch.cuda.current_stream() per hand-off (_stream's comment has the price)."""
+    __slots__ = ("side", "reads", "_scope")
+
+    def __init__(self, side, *reads):
+        self.side, self.reads = side, reads
+
+    def __enter__(self):
+        side = self.side
+        cur = torch.cuda.current_stream(side.device)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        side.wait_event(ready)
+        self._scope = torch.cuda.stream(side)
+        self._scope.__enter__()
+        return cur
+
+    def __exit__(self, *exc):
+        self._scope.__exit__(*exc)
+        for t in self.reads:
+            t.record_stream(self.side)
+        return False
+
+
 class KernelProbe:
     """Brackets every launch of one kernel family with HIP events on the launch stream (bench.py's roofline leg).
     `units` is the algorithmic work of the launch (FLOPs for the GEMM)."""

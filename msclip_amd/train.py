@@ -30,6 +30,7 @@ from . import comm as C
 from . import hip
 from . import gradgemm
 from . import options
+from .engine import Captions
 from .gradgemm import dgrad as _dgrad, wgrad as _wgrad, wgrad_async as _wgrad_async
 from .train_conv import ConvSideBackward, ConvSideBatchNorm
 
@@ -134,6 +135,15 @@ class TrainStep:
         self.ema_shadow = self._ema.views if self._ema else None      # {name: fp32 view of the arena}, named_parameters() order
         self.ema_updates = 0
         self._ema_assigned = False
+        self._ema_conv_pack = None           # the engine's conv_pack kind at ema_assign(): ema_resume() repeats a table re-pack
+        self.saved = None                    # activations of a forward() that backward() has not consumed yet
+        self.reducer = None                  # comm.GradReducer of the last backward() (None at world size 1)
+        self._plan = None                    # the optimizer launch's tensor table (_adamw_plan)
+        self._acc = None                     # accumulate()'s persistent gradient accumulators (_Accumulators)
+        self._wt_plan = None                 # hip.TransposePlan of the backward's W^T operands
+        self.schedule = None                 # learning-rate schedule (from_config sets it; set_epoch applies it)
+        self._base_lr = None                 # (lr, lr_share) before the schedule first touched them
+        self.phase_events = None             # tools/accumulate_bench.py sets []: _mark() appends (name, timing event)
         self._dp_gen = None
         if self.drop_path:
             self._dp_gen = torch.Generator(device=self.dev)
@@ -161,20 +171,14 @@ class TrainStep:
 
     # ------------------------------------------------------------------ forward that keeps what the backward needs
     @hip.off_default_stream
-    def forward(self, img, tok, drop_masks=None):
+    def forward(self, img, tok, drop_masks=None, _head=True, _update_stats=True):
         """drop_masks: replay these keep masks (drop_mask_shape(batch), bool) instead of drawing a set -- also with
         drop_path 0, where kept rows then carry the scale 1.0 exactly.  The masks used are left in self.last_drop_masks
-        (None when the step runs without stochastic depth)."""
-        self._ema_live("forward")
-        try:
-            return self._forward(img, tok, drop_masks=drop_masks)
-        finally:
-            self.eng.force_unfused = False
-
-    def _forward(self, img, tok, head=True, update_stats=True, drop_masks=None):
-        """head=False (accumulate()): stop in front of the contrastive head and return the two gather payloads; the saved
-        activations then wait for a backward(_dfeat=...).  update_stats=False: train-mode BatchNorm normalises with the
+        (None when the step runs without stochastic depth).
+        _head=False (accumulate() only): stop in front of the contrastive head and return the two gather payloads; the saved
+        activations then wait for a backward(_dfeat=...).  _update_stats=False: train-mode BatchNorm normalises with the
         batch statistics but leaves the module's running statistics alone (accumulate()'s feature pass)."""
+        self._ema_live("forward")
         e = self.eng
         e.refresh()
         with torch.cuda.device(e.dev), torch.no_grad():
@@ -187,10 +191,7 @@ class TrainStep:
             self.last_drop_masks = drop_masks
             if e.Lv > hip.ATTENTION_BWD_MAX_L or e.Lt > hip.ATTENTION_BWD_MAX_L:
                 raise NotImplementedError(f"msclip_attention_bwd covers sequences up to {hip.ATTENTION_BWD_MAX_L} tokens")
-            prev = getattr(self, "saved", None)
-            if prev is not None:                                   # a forward that was never differentiated: release its maps
-                prev["w"].pop("held", None)
-                self.saved = None
+            self._release_saved()                                  # a forward that was never differentiated: release its maps
             w = e._workspace(Bi, Bt)
             # the conv side's maps (w["stem"], w["par"], w["pool"], S1, P0) -- or the patch-conv model's patch matrix
             # w["PATCH"] -- are read again by backward(): until then the engine's inference entry points (an eval / logging
@@ -198,7 +199,6 @@ class TrainStep:
             w["held"] = True
             # captions run packed like the inference path (engine.text_pack_enabled): rows behind a caption's EOT position
             # neither influence an output nor receive a gradient.  `tok` may be a batch staged ahead (engine.stage_captions).
-            from .engine import Captions
             pack = e.text_pack_enabled()
             cap = tok if isinstance(tok, Captions) else None
             tokc = cap.tok if cap is not None else e._check_tok(tok)
@@ -216,7 +216,6 @@ class TrainStep:
             # ---- fronts (the conv side's maps stay in the workspace `w`; the tokens in front of ln_pre are cloned)
             keep = []
             sv["img"] = e._check_img(img)
-            e.force_unfused = True                   # layer-by-layer conv side: every map the backward reads stays in `w`
             cb = None
             if self.bn == "batch" and not e.patch:             # (the patch-conv model has no BatchNorm: bn is moot there)
                 if self.convbn is None:
@@ -224,28 +223,24 @@ class TrainStep:
                 cb = self.convbn
                 cb.begin(sv["img"], w, Bi)
                 cb.front()
-            e._vision_front(sv["img"], w, Bi, keep_pre=keep, convs_done=cb is not None)
+            # unfused=True at every engine call: the conv side runs layer by layer, every map the backward reads stays in `w`
+            e._vision_front(sv["img"], w, Bi, keep_pre=keep, convs_done=cb is not None, unfused=True)
             sv["tok_pre"] = keep[0]
             g2 = e.g * e.g
             # frozen statistics: the image-only conv branch + the adapters' top-down halves on the engine's side stream, as in
-            # the inference schedule (layer by layer: force_unfused keeps every map the backward reads in the workspace)
+            # the inference schedule (same-box A/B: 89.6-90.2 -> 88.5-88.9 ms per step)
             conv_events = None
-            # (same-box A/B: 89.6-90.2 -> 88.5-88.9 ms per step)
-            if (cb is None and not e.patch and not gradgemm._ranks_share_a_gpu() and not options.TRAIN.wgrad_sync
-                    and e.lateral == sorted(e.lateral)):
-                conv_events = e._conv_branch_on_side_stream(w, Bi)
-            if (cb is not None and conv_events is None and not gradgemm._ranks_share_a_gpu() and not options.TRAIN.wgrad_sync
-                    and e.lateral == sorted(e.lateral)):
+            side_ok = not e.patch and gradgemm.lane_enabled() and e.lateral == sorted(e.lateral)
+            if side_ok and cb is None:
+                conv_events = e._conv_branch_on_side_stream(w, Bi, unfused=True)
+            elif side_ok:
                 # train-mode BatchNorm: the same for the raw-conv -> statistics -> normalise chains of the parallel branch and
                 # the adapters' top-down halves (they depend on the image only)
                 if w["Ts"] is None:
                     w["Ts"] = [torch.empty(Bi * g2, D, dtype=F32, device=e.dev) for _ in e.adapters]
-                cur, side = torch.cuda.current_stream(e.dev), C.side_stream(e.dev)
-                ready = torch.cuda.Event()
-                ready.record(cur)
-                side.wait_event(ready)
+                side = C.side_stream(e.dev)
                 conv_events = []
-                with torch.cuda.stream(side):
+                with hip.forked(side):
                     for j in range(len(e.adapters)):
                         cb.stage(j)
                         cb.adapter_top(j, w["Ts"][j])
@@ -290,7 +285,7 @@ class TrainStep:
                         torch.cuda.current_stream(e.dev).wait_event(conv_events[j])
                         hip.adapter_sum(Xc[:Mv], w["Ts"][j], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
                     else:
-                        e._parallel_stage(j, w, Bi)
+                        e._parallel_stage(j, w, Bi, unfused=True)
                         hip.dwpool(w["par"][j], a["pool"], w["pool"][j], Bi, e.par_hw[j], e.par_hw[j], a["C"], a["k"])
                         hip.gemm(w["pool"][j], a["pw"].weight, w["T"], M=Bi * g2, N=a["pw"].cout, bias=a["pw"].bias, ldx=a["pw"].cin)
                         hip.adapter_sum(Xc[:Mv], w["T"], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
@@ -380,27 +375,18 @@ class TrainStep:
                 L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao, lno2=lno2, h=h, hid=hid)
                 sv["layers"][i] = L
                 Xc = XN
-            e.force_unfused = False
-            if cb is not None and update_stats:
+            if cb is not None and _update_stats:
                 cb.update_running_stats()
             # ---- heads + loss
             if sv.get("compact") is not None:
                 # the heads read the compact matrix of the last block's live rows (image cls rows, then EOT rows)
                 sv["x_out"] = sv["compact"]
-                xc_own, w["XC"] = w["XC"], sv["compact"]
-                try:
-                    e._head_image(w, Bi, compact=True)
-                    e._head_text(w, Bt, compact=True, Bi=Bi)
-                finally:
-                    w["XC"] = xc_own
+                e._head_image(w, Bi, compact=True, x=sv["compact"])
+                e._head_text(w, Bt, compact=True, Bi=Bi, x=sv["compact"])
             else:
                 sv["x_out"] = Xc if Xc is not X else X[:M].clone()
-                w["X"] = Xc                              # the heads read the final residual matrix
-                try:
-                    e._head_image(w, Bi)
-                    e._head_text(w, Bt)
-                finally:
-                    w["X"] = X
+                e._head_image(w, Bi, x=Xc)               # the heads read the final residual matrix
+                e._head_text(w, Bt, x=Xc)
             sv.update(hv=w["hv"].clone(), ht=w["ht"].clone(), fv_raw=w["fv_raw"].clone(), ft_raw=w["ft_raw"].clone(),
                       fv=w["fv"].clone(), ft=w["ft"].clone(), fvb=w["fvb"].clone(), ftb=w["ftb"].clone(), eot=w["eot"].clone())
             # ---- loss.  The inference path forms its logits from bf16 unit features (error ~0.03 on a logit at T = 1/0.07:
@@ -418,7 +404,7 @@ class TrainStep:
             s_dev = e.model.logit_scale.detach().float().exp()
             sv["scale"] = s_dev
             pi, pt = split(sv["fv"] * s_dev), split(sv["ft"])
-            if not head:
+            if not _head:
                 self.saved = sv
                 return pi, pt
             if C.comm.collectives:
@@ -432,19 +418,11 @@ class TrainStep:
             off = C.local_label_offset(Bi) if n > Bi else 0
             sv["off"], sv["n"] = off, n
             sv["allI"], sv["allT"] = allpi[:, :E].contiguous(), allpt[:, :E].contiguous()     # hi parts: dgrad operands (allI scaled)
-
-            def logits_block(a, ball):                                                         # A_loc @ B_all^T, fp32 (scale in the image side)
-                a3 = torch.cat([a[:, :E], a[:, :E], a[:, E:]], dim=1)
-                b3 = torch.cat([ball[:, :E], ball[:, E:], ball[:, :E]], dim=1)
-                S = torch.empty(a.shape[0], n, dtype=F32, device=e.dev)
-                hip.gemm(a3, b3, S)
-                return S
-            S_i, S_t = logits_block(pi, allpt), logits_block(pt, allpi)                        # image rows / caption rows
+            S_i = _logits(*_logit_operands(pi, allpt, E))                                      # image rows (they carry the scale)
+            S_t = _logits(*_logit_operands(pt, allpi, E))                                      # caption rows
             lse = torch.empty(2, Bi, dtype=F32, device=e.dev)
-            hip.lse_rows(S_i, lse[0])
-            hip.lse_rows(S_t, lse[1])
             out = torch.empty(1, dtype=F32, device=e.dev)
-            hip.clip_loss_partial(lse[0], lse[1], S_i, off, 1.0 / (2.0 * n), out)
+            _loss_partial(S_i, S_t, lse[0], lse[1], off, n, out)
             sv["coll"] = n > Bi or C.comm.collectives
             if sv["coll"]:
                 dist.all_reduce(out)
@@ -472,7 +450,7 @@ class TrainStep:
         gradients are fresh tensors either way.
         _dfeat (accumulate() only): (d loss / d image features, d loss / d text features, d loss / d logit_scale) of a
         forward that stopped in front of the head; the head's own backward is skipped, everything below it is the same."""
-        e, sv = self.eng, getattr(self, "saved", None)
+        e, sv = self.eng, self.saved
         if sv is None:
             raise RuntimeError("TrainStep.backward() needs the activations of a TrainStep.forward() that has not been "
                                "differentiated yet (call forward first; one backward per forward)")
@@ -586,31 +564,27 @@ class TrainStep:
             # step), all of them up front on the lane stream with this library's transpose kernel, last block first, one event
             # per block -- not four ATen transposed copies per block on the main queue (74 launches, 1.8 ms per step)
             wts, wt_ready = {}, {}
-            if not (options.TRAIN.wgrad_sync or gradgemm._ranks_share_a_gpu()):
-                cur_s, ln_s = torch.cuda.current_stream(dev), gradgemm.lane(dev)
-                ev0 = torch.cuda.Event()
-                ev0.record(cur_s)
-                ln_s.wait_event(ev0)
+            if gradgemm.lane_enabled():
                 sets = []
                 for i in reversed(range(e.n_layers)):
                     for blk in (e.tblk[i], e.vblk[i]):
                         if blk is not None and all(blk["w"] is not b for b in sets):
                             sets.append(blk["w"])
                 srcs = [t for bw in sets for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv)]
-                multi = all(t.shape[0] % 64 == 0 for t in srcs)
-                with torch.cuda.stream(ln_s):
-                    if multi:
+                ln_s = gradgemm.lane(dev)
+                with hip.forked(ln_s) as cur_s:
+                    if all(t.shape[0] % 64 == 0 for t in srcs):
                         # ONE table-driven launch for all of them (48 launches one by one kept the host busy for 0.6 ms at the start
                         # of the backward, the main queue idle behind it); the table lives while the packed weights do not move
-                        plan = getattr(self, "_wt_plan", None)
+                        plan = self._wt_plan
                         if plan is None or plan.key != tuple(t.data_ptr() for t in srcs):
                             plan = self._wt_plan = hip.TransposePlan(srcs)
                         outs = plan.run()
-                        ready = torch.cuda.Event()
-                        ready.record(ln_s)
+                        done = torch.cuda.Event()
+                        done.record(ln_s)
                         for j, bw in enumerate(sets):
                             wts[id(bw)] = tuple(outs[4 * j:4 * j + 4])
-                            wt_ready[id(bw)] = ready             # (one launch, one event: whichever weight set is asked for first waits for it)
+                            wt_ready[id(bw)] = done              # (one launch, one event: whichever weight set is asked for first waits for it)
                     else:
                         for bw in sets:
                             wts[id(bw)] = tuple(hip.transpose_bf16(t, t.shape[0], t.shape[0]) for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv))
@@ -853,8 +827,7 @@ class TrainStep:
                 conv.stem(grads, dtok)
             flush_wgrads()
             gradgemm.join(dev)                                   # the gradients queued on the lane stream
-            sv["w"].pop("held", None)
-            self.saved = None
+            self._release_saved()
             return reducer.finish(clone=clone) if reducer is not None else dict(grads)
 
     def _patch_wgrad(self, grads, dtok, patch, Bi):
@@ -912,86 +885,6 @@ class TrainStep:
             raise ValueError("TrainStep.accumulate() needs at least one (img, tok) chunk")
         if drop_masks is not None and len(drop_masks) != K:
             raise ValueError(f"TrainStep.accumulate(): {len(drop_masks)} drop_masks for {K} chunks")
-        try:
-            return self._accumulate(chunks, K, clone, check_features, drop_masks)
-        finally:
-            self.eng.force_unfused = False
-
-    def _release_saved(self):
-        sv = getattr(self, "saved", None)
-        if sv is not None:
-            sv["w"].pop("held", None)
-            self.saved = None
-
-    def _feature_pass(self, chunks, masks=None):
-        """Pass 1 of accumulate(): -> (bank_i, bank_t bf16 [N, 2E], [first row of every chunk] + [N]).  masks[k]: chunk k's
-        stochastic-depth keep masks (None: off)."""
-        e = self.eng
-        masks = masks if masks is not None else [None] * len(chunks)
-        sizes = [int(chunks[k][0].shape[0]) for k in range(len(chunks))]
-        starts = [0]
-        for b in sizes:
-            starts.append(starts[-1] + b)
-        N = starts[-1]
-        bank_i = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
-        bank_t = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
-        for k in range(len(chunks)):
-            img, tok = chunks[k]
-            pi, pt = self._forward(img, tok, head=False, update_stats=False, drop_masks=masks[k])
-            self._release_saved()                                                # nothing is kept for a backward
-            bank_i[starts[k]:starts[k + 1]] = pi
-            bank_t[starts[k]:starts[k + 1]] = pt
-        return bank_i, bank_t, starts
-
-    def _bank_head(self, bank_i, bank_t, starts):
-        """Pass 2 of accumulate(): -> (loss, [(d image features, d text features, d logit_scale) per chunk])."""
-        e = self.eng
-        dev, E = e.dev, e.E
-        with torch.cuda.device(dev), torch.no_grad():
-            N, K = starts[-1], len(starts) - 1
-            s_dev = e.model.logit_scale.detach().float().exp()
-            a3 = [torch.cat([b[:, :E], b[:, :E], b[:, E:]], dim=1) for b in (bank_i, bank_t)]       # [hi | hi | lo]
-            b3 = [torch.cat([b[:, :E], b[:, E:], b[:, :E]], dim=1) for b in (bank_i, bank_t)]       # [hi | lo | hi]
-            allI, allT = bank_i[:, :E].contiguous(), bank_t[:, :E].contiguous()
-
-            def blocks(k):                                                       # S_i, S_t [B_k, N]: the N x N matrix never exists
-                r0, r1 = starts[k], starts[k + 1]
-                S_i = torch.empty(r1 - r0, N, dtype=F32, device=dev)
-                S_t = torch.empty(r1 - r0, N, dtype=F32, device=dev)
-                hip.gemm(a3[0][r0:r1], b3[1], S_i)
-                hip.gemm(a3[1][r0:r1], b3[0], S_t)
-                return S_i, S_t
-            lse = torch.empty(2, N, dtype=F32, device=dev)
-            parts = torch.empty(K, dtype=F32, device=dev)
-            kept = None
-            for k in range(K):
-                r0, r1 = starts[k], starts[k + 1]
-                S_i, S_t = blocks(k)
-                hip.lse_rows(S_i, lse[0][r0:r1])
-                hip.lse_rows(S_t, lse[1][r0:r1])
-                hip.clip_loss_partial(lse[0][r0:r1], lse[1][r0:r1], S_i, r0, 1.0 / (2.0 * N), parts[k:k + 1])
-                if K == 1:
-                    kept = (S_i, S_t)
-            loss = parts[0].clone() if K == 1 else parts.sum()
-            npad = (N + 63) // 64 * 64
-            bt_T, bt_I = hip.transpose_bf16(allT, N, npad), hip.transpose_bf16(allI, N, npad)
-            dfeat = []
-            for k in range(K):
-                r0, r1 = starts[k], starts[k + 1]
-                S_i, S_t = kept if kept is not None else blocks(k)               # recomputed: the same bits (deterministic GEMM)
-                dfi, dft, dscale = _clip_head_bwd(e, S_i, S_t, allI, allT, lse[:, r0:r1], lse, r0, N, s_dev, bt=(bt_T, bt_I))
-                dfeat.append((dfi, dft, dscale.reshape(())))
-            return loss, dfeat
-
-    def _mark(self, name):
-        """tools/accumulate_bench.py sets self.phase_events = []: a timing event at every phase boundary of accumulate()."""
-        ev_list = getattr(self, "phase_events", None)
-        if ev_list is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record(torch.cuda.current_stream(self.eng.dev))
-            ev_list.append((name, ev))
-
-    def _accumulate(self, chunks, K, clone, check_features, drop_masks=None):
         e = self.eng
         self._mark("start")
         if drop_masks is not None:
@@ -1009,7 +902,7 @@ class TrainStep:
             bank_i = bank_t = None
         for k in range(K):
             img, tok = chunks[k]
-            pi, pt = self._forward(img, tok, head=False, drop_masks=masks[k])
+            pi, pt = self.forward(img, tok, drop_masks=masks[k], _head=False)
             if check_features:
                 r0, r1 = starts[k], starts[k + 1]
                 for name, now, banked in (("image", pi, bank_i[r0:r1]), ("text", pt, bank_t[r0:r1])):
@@ -1021,7 +914,7 @@ class TrainStep:
             del pi, pt
             g = self.backward(_dfeat=dfeat[k])
             dfeat[k] = None
-            acc = getattr(self, "_acc", None)
+            acc = self._acc
             if acc is None or acc.shapes != {key: (tuple(t.shape), t.device) for key, t in g.items()}:
                 acc = self._acc = _Accumulators(g)
             with torch.cuda.device(e.dev):
@@ -1033,14 +926,80 @@ class TrainStep:
         out = acc.views
         return loss, ({key: t.clone() for key, t in out.items()} if clone else dict(out))
 
+    def _release_saved(self):
+        if self.saved is not None:
+            self.saved["w"].pop("held", None)
+            self.saved = None
+
+    def _feature_pass(self, chunks, masks=None):
+        """Pass 1 of accumulate(): -> (bank_i, bank_t bf16 [N, 2E], [first row of every chunk] + [N]).  masks[k]: chunk k's
+        stochastic-depth keep masks (None: off)."""
+        e = self.eng
+        masks = masks if masks is not None else [None] * len(chunks)
+        sizes = [int(chunks[k][0].shape[0]) for k in range(len(chunks))]
+        starts = [0]
+        for b in sizes:
+            starts.append(starts[-1] + b)
+        N = starts[-1]
+        bank_i = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
+        bank_t = torch.empty(N, 2 * e.E, dtype=BF, device=e.dev)
+        for k in range(len(chunks)):
+            img, tok = chunks[k]
+            pi, pt = self.forward(img, tok, drop_masks=masks[k], _head=False, _update_stats=False)
+            self._release_saved()                                                # nothing is kept for a backward
+            bank_i[starts[k]:starts[k + 1]] = pi
+            bank_t[starts[k]:starts[k + 1]] = pt
+        return bank_i, bank_t, starts
+
+    def _bank_head(self, bank_i, bank_t, starts):
+        """Pass 2 of accumulate(): -> (loss, [(d image features, d text features, d logit_scale) per chunk])."""
+        e = self.eng
+        dev, E = e.dev, e.E
+        with torch.cuda.device(dev), torch.no_grad():
+            N, K = starts[-1], len(starts) - 1
+            s_dev = e.model.logit_scale.detach().float().exp()
+            a3_i, b3_t = _logit_operands(bank_i, bank_t, E)
+            a3_t, b3_i = _logit_operands(bank_t, bank_i, E)
+            allI, allT = bank_i[:, :E].contiguous(), bank_t[:, :E].contiguous()
+
+            def blocks(k):                                                       # S_i, S_t [B_k, N]: the N x N matrix never exists
+                r0, r1 = starts[k], starts[k + 1]
+                return _logits(a3_i[r0:r1], b3_t), _logits(a3_t[r0:r1], b3_i)
+            lse = torch.empty(2, N, dtype=F32, device=dev)
+            parts = torch.empty(K, dtype=F32, device=dev)
+            kept = None
+            for k in range(K):
+                r0, r1 = starts[k], starts[k + 1]
+                S_i, S_t = blocks(k)
+                _loss_partial(S_i, S_t, lse[0][r0:r1], lse[1][r0:r1], r0, N, parts[k:k + 1])
+                if K == 1:
+                    kept = (S_i, S_t)
+            loss = parts[0].clone() if K == 1 else parts.sum()
+            npad = (N + 63) // 64 * 64
+            bt_T, bt_I = hip.transpose_bf16(allT, N, npad), hip.transpose_bf16(allI, N, npad)
+            dfeat = []
+            for k in range(K):
+                r0, r1 = starts[k], starts[k + 1]
+                S_i, S_t = kept if kept is not None else blocks(k)               # recomputed: the same bits (deterministic GEMM)
+                dfi, dft, dscale = _clip_head_bwd(e, S_i, S_t, allI, allT, lse[:, r0:r1], lse, r0, N, s_dev, bt=(bt_T, bt_I))
+                dfeat.append((dfi, dft, dscale.reshape(())))
+            return loss, dfeat
+
+    def _mark(self, name):
+        """tools/accumulate_bench.py sets self.phase_events = []: a timing event at every phase boundary of accumulate()."""
+        if self.phase_events is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(torch.cuda.current_stream(self.eng.dev))
+            self.phase_events.append((name, ev))
+
     # ------------------------------------------------------------------ optimizer
     def set_epoch(self, epoch):
         """Apply the yaml's learning-rate schedule (self.schedule, train.from_config) for `epoch` to both parameter groups'
         base rates; the next step() re-points the optimizer table's rates.  No-op without a schedule."""
-        sch = getattr(self, "schedule", None)
+        sch = self.schedule
         if sch is None:
             return
-        if not hasattr(self, "_base_lr"):
+        if self._base_lr is None:
             self._base_lr = (self.lr, self.lr_share)
         base, base_sh = self._base_lr
         self.lr = sch.lr_at(base, epoch)
@@ -1072,7 +1031,7 @@ class TrainStep:
         rebuilt when the set of gradients changes, the optimizer state is replaced or the engine has re-packed (new copies)."""
         pk_ok = not self.eng.fp8
         sig = (id(self.eng.tblk[0]["w"].wqkv), pk_ok, id(self.state), self.eng.tensor_identity(), self.optimizer, self.always_adapt)
-        plan = getattr(self, "_plan", None)
+        plan = self._plan
         if plan is not None and plan.sig == sig and len(grads) == plan.ngrads and \
                 all(k in grads and grads[k].dtype == F32 and grads[k].numel() == n for k, n in plan.names.items()):
             # same tensors, this step's gradients (fresh allocations on one GPU, the bucket slots at N > 1); the few that
@@ -1141,7 +1100,7 @@ class TrainStep:
         """Names of the parameters whose gradient of the LAST step() held a NaN or an Inf (more precisely: whose chunks of the
         norm's table hold a non-finite partial sum of squares), in the table's order; [] where the step was clean.
         Synchronises (reads the optimizer table's partials); valid until the next step()."""
-        plan = getattr(self, "_plan", None)
+        plan = self._plan
         if self.nonfinite is None or plan is None or plan.partials is None:
             raise RuntimeError("TrainStep.nonfinite_gradients() needs TrainStep(..., nonfinite=...) and a step() before it")
         return nonfinite_names(plan.partials[:plan.n_partials].cpu(), list(plan.names.items()))
@@ -1285,6 +1244,27 @@ class TrainStep:
             finally:
                 self.ema_resume()
         return scope()
+
+
+def _logit_operands(a, ball, E):
+    """The K = 3E operand pair of the logits A_loc @ B_all^T from two gather payloads [rows, 2E] (bf16 hi | lo parts of the
+    fp32 features): [hi | hi | lo] of a, [hi | lo | hi] of ball -- hi.hi + hi.lo + lo.hi in one GEMM."""
+    return (torch.cat([a[:, :E], a[:, :E], a[:, E:]], dim=1), torch.cat([ball[:, :E], ball[:, E:], ball[:, :E]], dim=1))
+
+
+def _logits(a3, b3):
+    """-> S = a3 @ b3^T, fp32 [rows of a3, rows of b3]."""
+    S = torch.empty(a3.shape[0], b3.shape[0], dtype=F32, device=a3.device)
+    hip.gemm(a3, b3, S)
+    return S
+
+
+def _loss_partial(S_i, S_t, lse_i, lse_t, off, n, out):
+    """Row blocks S_i / S_t [R, n] (labels off .. off + R) -> their log-sum-exps into lse_i / lse_t [R] and their share of the
+    symmetric cross-entropy over n pairs into out [1]."""
+    hip.lse_rows(S_i, lse_i)
+    hip.lse_rows(S_t, lse_t)
+    hip.clip_loss_partial(lse_i, lse_t, S_i, off, 1.0 / (2.0 * n), out)
 
 
 def _clip_head_bwd(e, S_i, S_t, allI, allT, lse_loc, lse_all, off, n, scale, bt=None):

@@ -17,8 +17,8 @@ on the FOLDED weight Wf = W * s, bf = beta - mean * s, s = gamma / sqrt(var + ep
 own parameters is a few per-channel vector operations (fold_grads).  The stem's 1x1 shortcut lives in the centre tap of
 its 3x3 (packing.stem_stage): its gradient is the centre tap of the merged filter's gradient.
 
-Activations are read from the engine's workspace (the training forward runs the conv side layer by layer with
-engine.force_unfused, so every intermediate map is there): valid until the next forward on the same batch shape.
+Activations are read from the engine's workspace (the training forward asks the engine for the conv side layer by layer,
+unfused=True, so every intermediate map is there): valid until the next forward on the same batch shape.
 """
 import torch
 
