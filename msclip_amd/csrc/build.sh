@@ -7,7 +7,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffast-math -fno-finite-math-o
 mkdir -p build
 objs=()
 pids=()
-for f in gemm gemm_small attention qkv_attention attention_bwd backward backward_conv rows conv front loss pack api plan comm optim clip ema probe; do
+for f in gemm gemm_small gemm_skinny attention qkv_attention attention_bwd backward backward_conv rows conv front loss pack api plan comm optim clip ema probe; do
   stale=0
   for d in $f.hip common.h gemm_epilogue.h plan.h multi_tensor.h ../../include/msclip_hip.h ../../include/msclip_ext.h ../../include/msclip_ext2.h ../../include/msclip_ext3.h ../../include/msclip_ext4.h ../../include/msclip_ext5.h; do
     if [ ! -f build/$f.o ] || [ $d -nt build/$f.o ]; then stale=1; fi

@@ -687,4 +687,218 @@ __device__ __forceinline__ void epilogue_generic16(f32x4 (&acc)[2 * TN][2 * TM],
   }
 }
 
+// ---- 32 x 32 accumulator tiles (v_mfma_f32_32x32x16_bf16 with swapped operands: gemm_kernel, gemm_skinny_kernel): a lane owns
+// row lane & 31 and the columns 8g + 4 (lane >> 5) + 0..3 of every 32-column tile.
+
+// Interior tile (no guards): transpose the wave's TM x TN 32x32 accumulator tiles through LDS so that 8 lanes
+// cover one 128-byte line of one output row; bias/QuickGELU are applied in accumulator layout, the residual
+// add / ReLU / conversion after the transpose (row-contiguous, full-line residual loads).
+// RS (msclip_gemm_rowscale: resid_kind 1, fp32 out, act 0, host-checked): out = resid + rscale[row] * v, and a row with scale 0
+// leaves as the residual itself.  The table travels in the kernel's COPY of the descriptor, in a member this form cannot use
+// (csum, the LayerNorm fold consumer's): the unscaled instantiations keep their signature and compile to what they were.
+template <int TM, int TN, bool RS = false>
+__device__ __forceinline__ void epilogue_interior(f32x16 (&acc)[TN][TM], const msclip_gemm_desc& a, char* stg,
+                                                  int mw0, int nw0, int lane) {
+  const float* __restrict__ rscale = RS ? a.csum : nullptr;
+  const int fr = lane & 31, fhi = lane >> 5;
+  const int srow = lane >> 3, sch = lane & 7;      // read-back mapping: row i*8 + srow, 16-byte chunk sch
+  const float* __restrict__ bias = a.bias;
+  float4 bv[TN][4];
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      bv[tn][g] = (bias && nw0 + fhi * 4 + tn * 32 + g * 8 < a.N) ? *(const float4*)(bias + nw0 + fhi * 4 + tn * 32 + g * 8)
+                                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool direct16 = TN == 2 && a.out_kind == 0 && a.resid_kind == 0;   // bf16 out, nothing to add after the transpose
+  char* wr = stg + fr * 128;
+  const int wsw = fr & 7;
+  const char* rd = stg + srow * 128 + ((sch ^ srow) << 4);      // + i * 1024 for row block i
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm) {
+    const int mrow0 = mw0 + tm * 32;
+    if (direct16) {                                  // 64 bf16 columns per staged row: TN == 2 only
+#pragma unroll
+      for (int tn = 0; tn < (TN == 2 ? TN : 0); ++tn)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float v0 = acc[tn][tm][g * 4 + 0] * a.alpha + bv[tn][g].x;
+          float v1 = acc[tn][tm][g * 4 + 1] * a.alpha + bv[tn][g].y;
+          float v2 = acc[tn][tm][g * 4 + 2] * a.alpha + bv[tn][g].z;
+          float v3 = acc[tn][tm][g * 4 + 3] * a.alpha + bv[tn][g].w;
+          if (a.act == 1) {
+            v0 = v0 / (1.f + __expf(-1.702f * v0)); v1 = v1 / (1.f + __expf(-1.702f * v1));
+            v2 = v2 / (1.f + __expf(-1.702f * v2)); v3 = v3 / (1.f + __expf(-1.702f * v3));
+          } else if (a.act == 2) {
+            v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
+          }
+          uint2 o;
+          o.x = pack_bf16x2(v0, v1);
+          o.y = pack_bf16x2(v2, v3);
+          const int c = tn * 4 + g;                                // 16-byte chunk; this lane owns half fhi of it
+          *(uint2*)(wr + ((c ^ wsw) << 4) + fhi * 8) = o;
+        }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint4 u = *(const uint4*)(rd + i * 1024);
+        if (nw0 + sch * 8 < a.N)   // N % 8 == 0 on this path
+          *(uint4*)((bf16_t*)a.out + (size_t)(mrow0 + i * 8 + srow) * a.ldo + nw0 + sch * 8) = u;
+      }
+    } else {
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float4 v;
+          v.x = acc[tn][tm][g * 4 + 0] * a.alpha + bv[tn][g].x;
+          v.y = acc[tn][tm][g * 4 + 1] * a.alpha + bv[tn][g].y;
+          v.z = acc[tn][tm][g * 4 + 2] * a.alpha + bv[tn][g].z;
+          v.w = acc[tn][tm][g * 4 + 3] * a.alpha + bv[tn][g].w;
+          if (a.act == 1) {
+            v.x = v.x / (1.f + __expf(-1.702f * v.x)); v.y = v.y / (1.f + __expf(-1.702f * v.y));
+            v.z = v.z / (1.f + __expf(-1.702f * v.z)); v.w = v.w / (1.f + __expf(-1.702f * v.w));
+          }
+          const int c = g * 2 + fhi;                               // 16-byte chunk = 4 fp32 columns
+          *(float4*)(wr + ((c ^ wsw) << 4)) = v;
+        }
+        float4 rv[4];
+        float rs[RS ? 4 : 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const size_t row = (size_t)(mrow0 + i * 8 + srow);
+          const int n = nw0 + tn * 32 + sch * 4;
+          if constexpr (RS) rs[i] = rscale[row];
+          if (n >= a.N) {
+            rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+          } else if (a.resid_kind == 1) {
+            rv[i] = *(const float4*)((const float*)a.resid + row * a.ldr + n);
+          } else if (a.resid_kind == 2) {
+            const uint2 u = *(const uint2*)((const bf16_t*)a.resid + row * a.ldr + n);
+            rv[i] = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
+                                __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+          } else {
+            rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float4 v = *(const float4*)(rd + i * 1024);
+          if constexpr (RS) {
+            const float s = rs[i];
+            v.x = s != 0.f ? rv[i].x + s * v.x : rv[i].x; v.y = s != 0.f ? rv[i].y + s * v.y : rv[i].y;
+            v.z = s != 0.f ? rv[i].z + s * v.z : rv[i].z; v.w = s != 0.f ? rv[i].w + s * v.w : rv[i].w;
+          } else {
+            v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;
+          }
+          if (a.act == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+          const size_t row = (size_t)(mrow0 + i * 8 + srow);
+          const int n = nw0 + tn * 32 + sch * 4;
+          if (n >= a.N) {
+          } else if (a.out_kind == 1) {
+            *(float4*)((float*)a.out + row * a.ldo + n) = v;
+          } else {
+            uint2 o;
+            o.x = pack_bf16x2(v.x, v.y);
+            o.y = pack_bf16x2(v.z, v.w);
+            *(uint2*)((bf16_t*)a.out + row * a.ldo + n) = o;
+          }
+        }
+      }
+    }
+  }
+}
+
+// Edge tiles, ragged N, unaligned leading dimensions, row scatter / table residual: guarded, straight from the
+// accumulator layout (lane owns row .. + (lane&31), columns .. + 8g + 4*(lane>>5) + 0..3).
+template <int TM, int TN, bool RS = false>
+__device__ __forceinline__ void epilogue_generic(f32x16 (&acc)[TN][TM], const msclip_gemm_desc& a, bool vec, int mw0,
+                                                 int nw0, int lane) {
+  const float* __restrict__ rscale = RS ? a.csum : nullptr;
+  const int fr = lane & 31, fhi = lane >> 5;
+  const float* __restrict__ bias = a.bias;
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm) {
+    const int m = mw0 + tm * 32 + fr;
+    if (m >= a.M) continue;
+    const int grp = m / a.rpg;
+    const size_t orow = (size_t)(m + grp * a.radd + a.roff);
+    size_t rrow = (size_t)m;
+    if (a.resid_kind == 3) rrow = (size_t)(m - grp * a.rpg + a.roff);
+    float rs = 1.f;
+    if constexpr (RS) rs = rscale[m];                // the launch's row, before the scatter
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = nw0 + tn * 32 + g * 8 + fhi * 4;
+        if (n >= a.N) continue;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = acc[tn][tm][g * 4 + j] * a.alpha;
+        if (vec) {
+          if (bias) {
+            const float4 bv = *(const float4*)(bias + n);
+            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
+          }
+          if (a.act == 1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = v[j] / (1.f + __expf(-1.702f * v[j]));
+          }
+          if constexpr (RS) {
+            const float4 rv = *(const float4*)((const float*)a.resid + rrow * a.ldr + n);
+            v[0] = rs != 0.f ? rv.x + rs * v[0] : rv.x; v[1] = rs != 0.f ? rv.y + rs * v[1] : rv.y;
+            v[2] = rs != 0.f ? rv.z + rs * v[2] : rv.z; v[3] = rs != 0.f ? rv.w + rs * v[3] : rv.w;
+          } else if (a.resid_kind == 1 || a.resid_kind == 3) {
+            const float4 rv = *(const float4*)((const float*)a.resid + rrow * a.ldr + n);
+            v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
+          } else if (a.resid_kind == 2) {
+            const uint2 rv = *(const uint2*)((const bf16_t*)a.resid + rrow * a.ldr + n);
+            v[0] += __uint_as_float(rv.x << 16); v[1] += __uint_as_float(rv.x & 0xffff0000u);
+            v[2] += __uint_as_float(rv.y << 16); v[3] += __uint_as_float(rv.y & 0xffff0000u);
+          } else if (a.resid_kind == 6) {        // accumulate: + the bf16 value already at the STORE row (in-place out += v)
+            const uint2 rv = *(const uint2*)((const bf16_t*)a.resid + orow * a.ldr + n);
+            v[0] += __uint_as_float(rv.x << 16); v[1] += __uint_as_float(rv.x & 0xffff0000u);
+            v[2] += __uint_as_float(rv.y << 16); v[3] += __uint_as_float(rv.y & 0xffff0000u);
+          } else if (a.resid_kind == 5) {        // ReLU backward: keep v where the saved activation (bf16, at the STORE row) is > 0
+            const uint2 rv = *(const uint2*)((const bf16_t*)a.resid + orow * a.ldr + n);
+            v[0] = __uint_as_float(rv.x << 16) > 0.f ? v[0] : 0.f; v[1] = __uint_as_float(rv.x & 0xffff0000u) > 0.f ? v[1] : 0.f;
+            v[2] = __uint_as_float(rv.y << 16) > 0.f ? v[2] : 0.f; v[3] = __uint_as_float(rv.y & 0xffff0000u) > 0.f ? v[3] : 0.f;
+          }
+          if (a.act == 2) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+          }
+          if (a.out_kind == 1) {
+            *(float4*)((float*)a.out + orow * a.ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
+          } else {
+            uint2 o;
+            o.x = pack_bf16x2(v[0], v[1]);
+            o.y = pack_bf16x2(v[2], v[3]);
+            *(uint2*)((bf16_t*)a.out + orow * a.ldo + n) = o;
+          }
+        } else {  // ragged N or unaligned leading dimensions: element-wise tail path
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (n + j >= a.N) break;
+            float y = v[j];
+            if (bias) y += bias[n + j];
+            if (a.act == 1) y = y / (1.f + __expf(-1.702f * y));
+            if constexpr (RS) {
+              const float r = ((const float*)a.resid)[rrow * a.ldr + n + j];
+              y = rs != 0.f ? r + rs * y : r;
+            } else
+            if (a.resid_kind == 1 || a.resid_kind == 3) y += ((const float*)a.resid)[rrow * a.ldr + n + j];
+            else if (a.resid_kind == 2) y += bf16_to_f32(((const bf16_t*)a.resid)[rrow * a.ldr + n + j]);
+            else if (a.resid_kind == 5) y = bf16_to_f32(((const bf16_t*)a.resid)[orow * a.ldr + n + j]) > 0.f ? y : 0.f;
+            else if (a.resid_kind == 6) y += bf16_to_f32(((const bf16_t*)a.resid)[orow * a.ldr + n + j]);
+            if (a.act == 2) y = fmaxf(y, 0.f);
+            if (a.out_kind == 1) ((float*)a.out)[orow * a.ldo + n + j] = y;
+            else ((bf16_t*)a.out)[orow * a.ldo + n + j] = f32_to_bf16(y);
+          }
+        }
+      }
+    }
+  }
+}
+
 }  // namespace

@@ -101,29 +101,76 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
   return r;
 }
 
-__device__ __forceinline__ float merged_lse(const float* pm, const float* ps, int nsplit) {
-  float m = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) m = fmaxf(m, pm[s]);
-  float t = 0.f;
-  for (int s = 0; s < nsplit; ++s) t += ps[s] * __expf(pm[s] - m);
+// ---- msclip_clip_loss_from_partials.  One workgroup of LOSS_NT threads; a group of G consecutive lanes (the smallest power of
+// two >= nsplit, at most 64) owns a row: lane j holds the (max, sum-exp) partial j of both directions (partials j + G, ... too
+// when nsplit > 64, merged online), the row's max and sum are xor-butterflies inside the group -- every lane of it ends with the
+// same bits, the same on every run -- and the group's first lane carries the row's term.  LOSS_NT / G rows form a pass, and the
+// loads of LOSS_U passes are issued together, so a launch is a few memory round trips, not one per row and split.  Which lane
+// adds which rows, and the order of the final fold, depend on (R, nsplit) only.
+constexpr int LOSS_NT = 1024, LOSS_U = 8;
+
+struct LsePart { float m, t; };
+
+template <int G>
+__device__ __forceinline__ LsePart lse_lane_partial(const float* __restrict__ pm, const float* __restrict__ ps, int nsplit, int j) {
+  const int jc = min(j, nsplit - 1);                   // unconditional loads (lanes past nsplit re-read the last split, then drop it)
+  const float vm = pm[jc], vt = ps[jc];
+  LsePart p;
+  p.m = j < nsplit ? vm : -INFINITY;
+  p.t = j < nsplit ? vt : 0.f;
+  if constexpr (G == 64)                               // (narrower groups exist only for nsplit <= G)
+    for (int s = j + G; s < nsplit; s += G) {
+      const float sm = pm[s], nm = fmaxf(p.m, sm);
+      if (nm > -INFINITY) p.t = p.t * __expf(p.m - nm) + ps[s] * __expf(sm - nm);
+      p.m = nm;
+    }
+  return p;
+}
+
+template <int G>
+__device__ __forceinline__ float lse_group_merge(LsePart p) {
+  float m = p.m;
+#pragma unroll
+  for (int o = G >> 1; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float t = p.m > -INFINITY ? p.t * __expf(p.m - m) : 0.f;      // an empty split (max -inf, sum 0) adds nothing
+#pragma unroll
+  for (int o = G >> 1; o >= 1; o >>= 1) t += __shfl_xor(t, o, 64);
   return m + __logf(t);
 }
 
 // out[0] = scale * sum_i (lse_img[i] - d_i) + (lse_txt[i] - d_i)
-__global__ __launch_bounds__(256) void loss_from_partials_kernel(const float* __restrict__ pm_i,
-                                                                 const float* __restrict__ ps_i,
-                                                                 const float* __restrict__ pm_t,
-                                                                 const float* __restrict__ ps_t,
-                                                                 const float* __restrict__ diag, int R, int nsplit,
-                                                                 float scale, float* __restrict__ out,
-                                                                 float* __restrict__ lse_out) {
-  __shared__ float sh[4];
+template <int G>
+__global__ __launch_bounds__(LOSS_NT) void loss_from_partials_kernel(const float* __restrict__ pm_i,
+                                                                     const float* __restrict__ ps_i,
+                                                                     const float* __restrict__ pm_t,
+                                                                     const float* __restrict__ ps_t,
+                                                                     const float* __restrict__ diag, int R, int nsplit,
+                                                                     float scale, float* __restrict__ out,
+                                                                     float* __restrict__ lse_out) {
+  __shared__ float sh[LOSS_NT / 64];
+  constexpr int RPP = LOSS_NT / G;                     // rows per pass
+  const int j = threadIdx.x & (G - 1), g = threadIdx.x / G;
   float s = 0.f;
-  for (int i = threadIdx.x; i < R; i += 256) {
-    const float li = merged_lse(pm_i + (size_t)i * nsplit, ps_i + (size_t)i * nsplit, nsplit);
-    const float lt = merged_lse(pm_t + (size_t)i * nsplit, ps_t + (size_t)i * nsplit, nsplit);
-    if (lse_out) { lse_out[i] = li; lse_out[R + i] = lt; }
-    s += (li - diag[i]) + (lt - diag[i]);
+  for (int i0 = 0; i0 < R; i0 += RPP * LOSS_U) {       // uniform trip count: every lane takes part in the shuffles
+    LsePart pi[LOSS_U], pt[LOSS_U];
+    float d[LOSS_U];
+#pragma unroll
+    for (int u = 0; u < LOSS_U; ++u) {
+      const int ic = min(i0 + u * RPP + g, R - 1);     // rows past R: a valid row, dropped below
+      pi[u] = lse_lane_partial<G>(pm_i + (size_t)ic * nsplit, ps_i + (size_t)ic * nsplit, nsplit, j);
+      pt[u] = lse_lane_partial<G>(pm_t + (size_t)ic * nsplit, ps_t + (size_t)ic * nsplit, nsplit, j);
+      d[u] = diag[ic];
+    }
+#pragma unroll
+    for (int u = 0; u < LOSS_U; ++u) {
+      const int i = i0 + u * RPP + g;
+      const float li = lse_group_merge<G>(pi[u]);
+      const float lt = lse_group_merge<G>(pt[u]);
+      if (j == 0 && i < R) {
+        if (lse_out) { lse_out[i] = li; lse_out[R + i] = lt; }
+        s += (li - d[u]) + (lt - d[u]);
+      }
+    }
   }
   s = block_reduce_sum(s, sh);
   if (threadIdx.x == 0) out[0] = s * scale;
@@ -206,8 +253,17 @@ extern "C" int msclip_clip_loss_from_partials(const float* pmax_img, const float
                                               float* out, float* lse_out, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_clip_loss_from_partials, stream, pmax_img, psum_img, pmax_txt, psum_txt, diag, R, nsplit, scale, out, lse_out);
   if (!pmax_img || !psum_img || !pmax_txt || !psum_txt || !diag || !out || R <= 0 || nsplit <= 0) return MSCLIP_EINVAL;
-  hipLaunchKernelGGL(loss_from_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pmax_img, psum_img,
-                     pmax_txt, psum_txt, diag, R, nsplit, scale, out, lse_out);
+#define LOSS_FP(G)                                                                                              \
+  hipLaunchKernelGGL(loss_from_partials_kernel<G>, dim3(1), dim3(LOSS_NT), 0, (hipStream_t)stream, pmax_img, psum_img, \
+                     pmax_txt, psum_txt, diag, R, nsplit, scale, out, lse_out)
+  if (nsplit <= 1) LOSS_FP(1);
+  else if (nsplit <= 2) LOSS_FP(2);
+  else if (nsplit <= 4) LOSS_FP(4);
+  else if (nsplit <= 8) LOSS_FP(8);
+  else if (nsplit <= 16) LOSS_FP(16);
+  else if (nsplit <= 32) LOSS_FP(32);
+  else LOSS_FP(64);
+#undef LOSS_FP
   return msclip_launch_status();
 }
 
