@@ -17,6 +17,7 @@ Control flow follows Transformer.forward (M.py:2388-2459): stem -> tokens ->
 for i in 1..11: [parallel stage + lateral adapter before blocks 2,4,6,8,10] ->
 block i; text block 0 is text-only.
 """
+import collections
 import os
 
 import torch
@@ -418,7 +419,7 @@ class Engine:
         M = M_rows                                           # (allocation size of everything below)
         w["X"] = buf(M, D, dtype=f32)
         w["LNO"], w["QKV"], w["AO"], w["HID"] = buf(M, D), buf(M, 3 * D), buf(M, D), buf(M, 4 * D)
-        # LayerNorm fold (_blocks_fold): per-row centre (the row's mean at the previous LayerNorm point), (rstd, mean * rstd) for
+        # LayerNorm fold (_blocks): per-row centre (the row's mean at the previous LayerNorm point), (rstd, mean * rstd) for
         # the consuming projection, the producing GEMM's per-64-column partial sums; which row segments hold produced operands
         w["CEN"], w["RST"], w["PART"] = buf(M, dtype=f32), buf(M, 2, dtype=f32), buf(M, D // 64, 2, dtype=f32)
         w["fold_pending"] = {"v": False, "t": False}
@@ -781,21 +782,49 @@ class Engine:
         taps[name] = out * live[:, :, None]
         taps["text_lengths"] = w["len"].clone()
 
-    def _last_block_attention(self, w, Bi, Bt, groups):
+    # ---- a layer's rows: one record per tower that runs, (.., row0, row1, block dict) -- the helpers below read the last three
+    #      fields, so they take plain (row0, row1, block dict) triples as well (the training forward's, the compact matrices')
+    Seg = collections.namedtuple("Seg", "tower folded r0 r1 blk")     # folded: LNO holds these rows' folded operand (_ln_1)
+
+    def _blk(self, i, tower):
+        return (self.vblk if tower == "v" else self.tblk)[i]
+
+    @staticmethod
+    def _live_segs(Bi, Bt, vb, tb):
+        """The segments of the compact matrices (XC / AOC / LNC ...): the images' class rows, then the captions' EOT rows."""
+        return ([(0, Bi, vb)] if Bi else []) + ([(Bi, Bi + Bt, tb)] if Bt else [])
+
+    @staticmethod
+    def _groups(segs):
+        """[(row0, row1, packed weights)] of a layer's projections: one launch over both towers' rows where the towers share the
+        block's tensors, else one per tower."""
+        if len(segs) == 2 and segs[0][-1]["w"] is segs[1][-1]["w"]:
+            return [(segs[0][-3], segs[1][-2], segs[0][-1]["w"])]
+        return [(r0, r1, b["w"]) for *_, r0, r1, b in segs]
+
+    @staticmethod
+    def _layernorm(segs, which, x, out):
+        """LayerNorm `which` ("ln1" / "ln2") of a layer's rows, x -> out (bf16): one launch over both towers' rows (own gamma /
+        beta per modality), or one per tower when only one runs."""
+        if len(segs) == 2:
+            (*_, r0, rs, vb), (*_, r1, tb) = segs
+            return hip.layernorm_split(x[r0:r1], vb[which].g, vb[which].b, tb[which].g, tb[which].b, rs - r0, out[r0:r1], r1 - r0)
+        for *_, r0, r1, b in segs:
+            hip.layernorm(x[r0:r1], b[which].g, b[which].b, out[r0:r1], r1 - r0)
+
+    def _last_block_attention(self, w, Bi, Bt, segs):
         """The last block's attention when only the class / EOT rows are read afterwards: keys and values are still projected
         for every token (the k | v two thirds of in_proj), the query only for the Bi + Bt live rows, and one query per
         sample attends (msclip_attention_lastq) straight into the compact matrix AOC."""
         D, Mv = self.D, w["Mv"]
         LNO, QKV, LNC, QC, AOC = w["LNO"], w["QKV"], w["LNC"], w["QC"], w["AOC"]
-        for r0, r1, bw in groups:
+        for r0, r1, bw in self._groups(segs):
             hip.gemm(LNO[r0:r1], bw.wqkv[D:], QKV[r0:r1, D:], bias=bw.bqkv[D:], mdev=self._md(w, r0, r1))
         if Bi:
             hip.gather_rows(LNO, LNC[:Bi], Bi, row_mul=self.Lv)
         if Bt:
             hip.gather_rows(LNO, LNC[Bi:], Bt, row_idx=w["eot"])
-        n = Bi + Bt
-        cgroups = [(0, n, groups[0][2])] if len(groups) == 1 else [(0, Bi, groups[0][2]), (Bi, n, groups[1][2])]
-        for r0, r1, bw in cgroups:
+        for r0, r1, bw in self._groups(self._live_segs(Bi, Bt, segs[0][-1], segs[-1][-1])):
             if r1 > r0:
                 hip.gemm(LNC[r0:r1], bw.wqkv[:D], QC[r0:r1], bias=bw.bqkv[:D])
         if Bi:
@@ -820,16 +849,11 @@ class Engine:
             hip.gather_rows(X, XC[Bi:], Bt, row_idx=w["eot"])
             if not attended:
                 hip.gather_rows(AO, AOC[Bi:], Bt, row_idx=w["eot"])
-        n = Bi + Bt
-        segs = ([(0, Bi, vb)] if Bi else []) + ([(Bi, n, tb)] if Bt else [])
-        groups = [(0, n, vb["w"])] if len(segs) == 2 and vb["w"] is tb["w"] else [(r0, r1, b["w"]) for r0, r1, b in segs]
+        segs = self._live_segs(Bi, Bt, vb, tb)
+        groups = self._groups(segs)
         for r0, r1, bw in groups:
             hip.gemm(AOC[r0:r1], bw.wo, XC[r0:r1], bias=bw.bo, resid=XC[r0:r1], resid_kind=hip.RESID_F32)
-        if len(segs) == 2:
-            hip.layernorm_split(XC[:n], vb["ln2"].g, vb["ln2"].b, tb["ln2"].g, tb["ln2"].b, Bi, LNC[:n], n)
-        else:
-            for r0, r1, b in segs:
-                hip.layernorm(XC[r0:r1], b["ln2"].g, b["ln2"].b, LNC[r0:r1], r1 - r0)
+        self._layernorm(segs, "ln2", XC, LNC)
         for r0, r1, bw in groups:
             hip.gemm(LNC[r0:r1], bw.wfc, HIDC[r0:r1], bias=bw.bfc, act=hip.ACT_QUICKGELU)
             hip.gemm(HIDC[r0:r1], bw.wpr, XC[r0:r1], bias=bw.bpr, resid=XC[r0:r1], resid_kind=hip.RESID_F32)
@@ -944,11 +968,11 @@ class Engine:
         rows (own gamma / beta per modality), or one per tower when only one runs."""
         X = w["X"]
         if len(segs) == 2:
-            (r0, rs, vb), (_, r1, tb) = segs
+            (*_, r0, rs, vb), (*_, r1, tb) = segs
             hip.layernorm_f8(X[r0:r1], vb[which].g, vb[which].b, tb[which].g, tb[which].b, rs - r0, w["LNQ"][r0:r1], w["RS"][r0:r1], r1 - r0,
                              mdev=self._md(w, r0, r1))
         else:
-            for r0, r1, b in segs:
+            for *_, r0, r1, b in segs:
                 hip.layernorm_f8(X[r0:r1], b[which].g, b[which].b, b[which].g, b[which].b, r1 - r0, w["LNQ"][r0:r1], w["RS"][r0:r1], r1 - r0,
                                  mdev=self._md(w, r0, r1))
 
@@ -968,7 +992,7 @@ class Engine:
         carry their 64^-0.5), csum = row sums of the bf16 values (what the MFMA contracts), bias' in fp32."""
         key = (i, tower, which)
         if key not in self._foldw:
-            blk = (self.vblk if tower == "v" else self.tblk)[i]
+            blk = self._blk(i, tower)
             bw, ln = blk["w"], blk["ln1" if which == "qkv" else "ln2"]
             W, b = (bw.wqkv, bw.bqkv) if which == "qkv" else (bw.wfc, bw.bfc)
             Wf = (W.float() * ln.g[None, :]).to(torch.bfloat16).contiguous()
@@ -1000,72 +1024,172 @@ class Engine:
         cu = torch.cat([t for t in (img, txt, end) if t is not None]).contiguous()
         return hip.QkvAttnTables(cu, Bi + Bt, split_sample=Bi if (Bi and Bt) else 0, total_rows=live)
 
-    def _fused_qkv_weights(self, i, tower, folded):
+    def _fused_qkv_weights(self, i, seg):
         """Head-major (weight, bias, csum) of layer i's in_proj for one tower's rows: gamma-folded (LNO holds x - centre) or
         plain (LNO holds the LayerNorm output; zero column sums)."""
-        key = (i, tower, "qkv_hm", folded)
+        key = (i, seg.tower, "qkv_hm", seg.folded)
         if key not in self._foldw:
-            if folded:
-                W, c, b = self._fold_weights(i, tower, "qkv")
+            if seg.folded:
+                W, c, b = self._fold_weights(i, seg.tower, "qkv")
             else:
-                bw = (self.vblk if tower == "v" else self.tblk)[i]["w"]
+                bw = seg.blk["w"]
                 W, b, c = bw.wqkv, bw.bqkv, torch.zeros(3 * self.D, dtype=torch.float32, device=self.dev)
             self._foldw[key] = hip.head_major_qkv(W, b, self.heads, c)
         return self._foldw[key]
 
-    def _fused_qkv_attention(self, w, i, r0, r1, modes, Bi, Bt):
-        """in_proj + attention of layer i over rows [r0, r1) = both towers (modes as in _fold_proj), one launch."""
+    def _fused_qkv_attention(self, w, i, r0, r1, segs, Bi, Bt):
+        """in_proj + attention of layer i over rows [r0, r1) = both towers, one launch.  segs as in _fold_proj; a single plain
+        segment stands for all rows (shared weights, no row statistics)."""
         if w.get("fused_tabs") is None:
             w["fused_tabs"] = self._fused_tables(w, Bi, Bt)
             if w["M"] > w["fused_tabs"].rowseg.shape[0]:
                 w["AO"][w["fused_tabs"].rowseg.shape[0]:w["M"]].zero_()     # tile padding behind the last caption: finite operand rows of out_proj
         Mv = w["Mv"]
-        W1, b1, c1 = self._fused_qkv_weights(i, modes[0][0], modes[0][3])
-        use_fold = any(m[3] for m in modes)
+        W1, b1, c1 = self._fused_qkv_weights(i, segs[0])
         fi = None
-        if len(modes) == 2:
-            W2, b2, c2 = self._fused_qkv_weights(i, modes[1][0], modes[1][3])
-            fi = hip.FoldIn(w["RST"][r0:r1], c1, W2, b2, c2, modes[1][1] - r0)
-        elif use_fold:
+        if len(segs) == 2:
+            W2, b2, c2 = self._fused_qkv_weights(i, segs[1])
+            fi = hip.FoldIn(w["RST"][r0:r1], c1, W2, b2, c2, segs[1].r0 - r0)
+        elif segs[0].folded:
             fi = hip.FoldIn(w["RST"][r0:r1], c1)
         assert r0 == 0
         hip.qkv_attention(w["LNO"][r0:r1], W1, b1, w["AO"][r0:r1], w["fused_tabs"], self.heads,
                           causal_from_row=Mv if Bt else hip.INT_MAX, fold_in=fi, M=r1 - r0)
 
-    def _fold_proj(self, w, i, which, r0, r1, modes, out, act):
-        """One projection over rows [r0, r1) behind a LayerNorm.  modes = [(tower, row0, row1, folded)]: a folded segment's rows
-        of LNO hold bf16 (x - centre) and take the gamma-folded weight; a plain segment's rows hold a LayerNorm output (RST rows
-        (1, 0)) and take the packed weight as it is."""
-        def seg_weights(tower, folded):
-            if folded:
-                return self._fold_weights(i, tower, which)
-            bw = (self.vblk if tower == "v" else self.tblk)[i]["w"]
-            W, b = (bw.wqkv, bw.bqkv) if which == "qkv" else (bw.wfc, bw.bfc)
+    def _fold_proj(self, w, i, which, r0, r1, segs, out, act):
+        """One projection ("qkv": in_proj, "fc": c_fc) over rows [r0, r1) behind a LayerNorm.  A folded segment's rows of LNO hold
+        bf16 (x - centre) and take the gamma-folded weight; a plain segment's rows hold a LayerNorm output (RST rows (1, 0)) and
+        take the packed weight as it is.  No folded segment: the plain GEMM."""
+        def packed(s):
+            bw = s.blk["w"]
+            return (bw.wqkv, bw.bqkv) if which == "qkv" else (bw.wfc, bw.bfc)
+
+        def seg_weights(s):
+            if s.folded:
+                return self._fold_weights(i, s.tower, which)
             if "zcs" not in self._foldw:
                 self._foldw["zcs"] = torch.zeros(4 * self.D, dtype=torch.float32, device=self.dev)
+            W, b = packed(s)
             return W, self._foldw["zcs"], b
         LNO, RST = w["LNO"], w["RST"]
         md = self._md(w, r0, r1)
-        if not any(m[3] for m in modes):
-            W, _, b = seg_weights(modes[0][0], False)
+        if not any(s.folded for s in segs):
+            W, b = packed(segs[0])
             return hip.gemm(LNO[r0:r1], W, out[r0:r1], bias=b, act=act, mdev=md)
-        W1, c1, b1 = seg_weights(modes[0][0], modes[0][3])
-        if len(modes) == 1:
+        W1, c1, b1 = seg_weights(segs[0])
+        if len(segs) == 1:
             fi = hip.FoldIn(RST[r0:r1], c1)
         else:
-            W2, c2, b2 = seg_weights(modes[1][0], modes[1][3])
-            fi = hip.FoldIn(RST[r0:r1], c1, W2, b2, c2, modes[1][1] - r0)
+            W2, c2, b2 = seg_weights(segs[1])
+            fi = hip.FoldIn(RST[r0:r1], c1, W2, b2, c2, segs[1].r0 - r0)
         return hip.gemm(LNO[r0:r1], W1, out[r0:r1], bias=b1, act=act, fold_in=fi, mdev=md)
 
-    def _blocks_fold(self, w, Bi, Bt, taps, conv_events, compact, layers):
-        """The layer loop with the LayerNorms folded into the GEMMs around them (DESIGN.md "LayerNorm fold"): out_proj and c_proj
-        write, beside the fp32 residual update, the bf16 operand of the projection that follows -- (x - centre[m]), the centre being
-        the row's mean one LayerNorm earlier -- and per-row partial sums; a one-thread-per-row kernel turns those into (rstd, mean
-        rstd); in_proj / c_fc apply them (and gamma / beta through their weights) to their accumulators.  The separate LayerNorm
-        passes over the token matrix (a 200 MB read + 100 MB write each) remain only where the rows come from somewhere else:
-        behind the stem / the embedding, behind a lateral adapter, and in the last block's live-row tail."""
-        Mv, M, D = w["Mv"], w["M"], self.D
-        X, LNO, QKV, AO, HID, CEN, RST, PART = (w[k] for k in ("X", "LNO", "QKV", "AO", "HID", "CEN", "RST", "PART"))
+    # ---- the layer loop (_blocks) and the three points where its two forms differ.  Folded (_fold_eligible; DESIGN.md "LayerNorm
+    #      fold"): out_proj and c_proj write, beside the fp32 residual update, the bf16 operand of the projection that follows --
+    #      (x - centre[m]), the centre being the row's mean one LayerNorm earlier -- and per-row partial sums; a one-thread-per-row
+    #      kernel turns those into (rstd, mean rstd); in_proj / c_fc apply them (and gamma / beta through their weights) to their
+    #      accumulators.  LayerNorm passes over the token matrix (a 200 MB read + 100 MB write each) remain only where the rows come
+    #      from somewhere else: behind the stem / the embedding, behind a lateral adapter, in the last block's live-row tail.
+    #      Plain: a LayerNorm pass per ln_1 / ln_2 (bf16, or e4m3 under PRECISION fp8 / fp8-qkv).
+    def _lateral(self, w, i, Bi, taps, conv_events, ln1=None):
+        """The lateral adapter in front of vision block i -- behind its conv stage, or behind the side stream's event when that
+        ran the stage: X[:Mv] -> XA.  ln1: _adapter's.  -> (src, raw) of ln_1, which reads the adapter output and moves it
+        back into X."""
+        j = self.lateral.index(i)
+        if conv_events is not None:
+            self._wait(torch.cuda.current_stream(self.dev), conv_events[j])
+            self._adapter(j, w, Bi, t=w["Ts"][j], ln1=ln1)
+        else:
+            self._parallel_stage(j, w, Bi)
+            self._adapter(j, w, Bi, ln1=ln1)
+        if taps is not None:
+            if j:
+                c3 = self.par_specs[j][3]
+                self._tap_nhwc(taps, f"parallel{j}", w["par"][j], Bi, c3.h_out, c3.cout)
+            self._tap_tokens(taps, f"adapter{j}", w["XA"], Bi, self.Lv)
+        w["fold_pending"]["v"] = False                       # (operands a c_proj produced for these rows are stale)
+        return w["XA"], w["X"][:w["Mv"]]
+
+    def _ln_1(self, w, fold, segs, src, raw, by_adapter):
+        """Point 1, where ln_1's operand comes from.  Folded: already in LNO where the previous c_proj produced it (seg.folded)
+        or the adapter applied ln_1 (by_adapter), a layernorm_stats pass per tower elsewhere.  Plain: one LayerNorm launch
+        (_layernorm; the adapter output is picked up from its own buffer), fp8-qkv: the e4m3 pass."""
+        X, LNO, Mv = w["X"], w["LNO"], w["Mv"]
+        if fold:
+            for s in segs:
+                x, back = (src, raw) if (s.tower == "v" and raw is not None) else (X[s.r0:s.r1], None)
+                if not s.folded and not (by_adapter and s.tower == "v"):
+                    hip.layernorm_stats(x, s.blk["ln1"].g, s.blk["ln1"].b, LNO[s.r0:s.r1], s.r1 - s.r0, w["CEN"][s.r0:s.r1],
+                                        w["RST"][s.r0:s.r1], raw_out=back, mdev=self._md(w, s.r0, s.r1))
+                w["fold_pending"][s.tower] = False
+        elif self.fp8_qkv:
+            if raw is not None:                              # the adapter's output moves back into the residual matrix first
+                hip.gather_rows(src, raw, Mv)
+            self._ln_f8(w, segs, "ln1")
+        elif raw is not None:
+            ln1 = segs[0].blk["ln1"]
+            hip.layernorm(src, ln1.g, ln1.b, LNO[:Mv], Mv, raw_out=raw)
+            self._layernorm(segs[1:], "ln1", X, LNO)
+        else:
+            self._layernorm(segs, "ln1", X, LNO)
+
+    def _rest_fold(self, w, i, r0, r1, bw, segs, by_adapter, produce):
+        """Points 2 and 3, folded, one launch group: out_proj produces ln_2's operands (by_adapter: its residual is XA for the
+        image rows), c_fc consumes them, c_proj produces the next block's ln_1 operands (produce).  PRECISION fp8: out_proj
+        plain (bf16), ln_2 as the e4m3 LayerNorm pass, MLP on the fp8 MFMA; a calibrated c_proj over whole tiles produces like
+        the bf16 one.  rowstat_finalize sits directly behind each producing GEMM."""
+        X, LNO, AO, HID, CEN, RST, PART = (w[k] for k in ("X", "LNO", "AO", "HID", "CEN", "RST", "PART"))
+        Mv, md = w["Mv"], self._md(w, r0, r1)
+
+        def fold_out(**kw):
+            return hip.FoldOut(LNO[r0:r1], CEN[r0:r1], PART[r0:r1], **kw)
+
+        def finalize():
+            hip.rowstat_finalize(PART[r0:r1], CEN[r0:r1], RST[r0:r1], r1 - r0, self.D, mdev=md)
+        if self.fp8:
+            hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=X[r0:r1], resid_kind=hip.RESID_F32, mdev=md)
+            self._ln_f8(w, segs, "ln2")
+            produce = produce and bw.hid_scale is not None and self._calib is None
+            self._mlp_f8(w, r0, r1, bw, fold_out=fold_out() if produce else None)
+        else:
+            xa = by_adapter and segs[0].tower == "v"         # (image rows come first: r0 == 0)
+            fo = fold_out(resid2=X[r0:r1], split=Mv) if xa and r1 > Mv else fold_out()
+            hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=w["XA"] if xa else X[r0:r1], resid_kind=hip.RESID_F32,
+                     fold_out=fo, mdev=md)
+            finalize()
+            self._fold_proj(w, i, "fc", r0, r1, [s._replace(folded=True) for s in segs], HID, hip.ACT_QUICKGELU)
+            hip.gemm(HID[r0:r1], bw.wpr, X[r0:r1], bias=bw.bpr, resid=X[r0:r1], resid_kind=hip.RESID_F32,
+                     fold_out=fold_out() if produce else None, mdev=md)
+        if produce:
+            finalize()
+            for s in segs:
+                w["fold_pending"][s.tower] = True
+
+    def _rest_plain(self, w, segs, groups):
+        """Points 2 and 3, plain: out_proj, one LayerNorm launch for ln_2 (_layernorm; PRECISION fp8: the e4m3 pass), c_fc and
+        c_proj (fp8: _mlp_f8).  No device-side row counts here (dynamic_rows needs the fold)."""
+        X, LNO, AO, HID = w["X"], w["LNO"], w["AO"], w["HID"]
+        for r0, r1, bw, _ in groups:
+            hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=X[r0:r1], resid_kind=hip.RESID_F32)
+        if self.fp8:
+            self._ln_f8(w, segs, "ln2")
+        else:
+            self._layernorm(segs, "ln2", X, LNO)
+        for r0, r1, bw, _ in groups:
+            if self.fp8:
+                self._mlp_f8(w, r0, r1, bw)
+            else:
+                hip.gemm(LNO[r0:r1], bw.wfc, HID[r0:r1], bias=bw.bfc, act=hip.ACT_QUICKGELU)
+                hip.gemm(HID[r0:r1], bw.wpr, X[r0:r1], bias=bw.bpr, resid=X[r0:r1], resid_kind=hip.RESID_F32)
+
+    def _blocks(self, w, Bi, Bt, taps=None, conv_events=None, compact=False, layers=None):
+        """The layer loop.  Per layer: the lateral adapter in front of a vision block, ln_1 (_ln_1), in_proj + attention -- or the
+        compact last block (_last_block_attention / _last_block_tail) --, then out_proj / ln_2 / MLP (_rest_fold per launch
+        group, or _rest_plain), then the taps.  fold: decided once per call; w["fold_pending"] says across calls which towers'
+        rows of LNO hold operands the previous c_proj produced."""
+        fold = self._fold_eligible(w, Bi, Bt)
+        Mv, M = w["Mv"], w["M"]
+        X, QKV, AO = w["X"], w["QKV"], w["AO"]
         pend = w["fold_pending"]
         n_last = self.n_layers - 1
         for i in (range(self.n_layers) if layers is None else layers):
@@ -1073,167 +1197,35 @@ class Engine:
             tb = self.tblk[i] if Bt else None
             if vb is None and tb is None:
                 continue
-            segs = ([("v", 0, Mv, vb)] if vb is not None else []) + ([("t", Mv, M, tb)] if tb is not None else [])
             last_live = i == n_last and compact
-            # --- ln_1: folded where the previous c_proj produced these rows' operands, a LayerNorm pass elsewhere
-            modes = []
-            xa_stream = False                               # the image rows' fp32 stream sits in XA until out_proj moves it back to X
-            for tower, r0, r1, b in segs:
-                src, raw = X[r0:r1], None
-                if tower == "v" and i in self.lateral:
-                    j = self.lateral.index(i)
-                    # the adapter applies ln_1 itself (rows in registers) unless this block's out_proj is not the producing kernel
-                    xa_stream = not last_live and not self.fp8 and not self.opt.adapter_ln1_pass
-                    ln1 = b["ln1"] if xa_stream else None
-                    if conv_events is not None:
-                        self._wait(torch.cuda.current_stream(self.dev), conv_events[j])
-                        self._adapter(j, w, Bi, t=w["Ts"][j], ln1=ln1)
-                    else:
-                        self._parallel_stage(j, w, Bi)
-                        self._adapter(j, w, Bi, ln1=ln1)
-                    if taps is not None:
-                        if j:
-                            c3 = self.par_specs[j][3]
-                            self._tap_nhwc(taps, f"parallel{j}", w["par"][j], Bi, c3.h_out, c3.cout)
-                        self._tap_tokens(taps, f"adapter{j}", w["XA"], Bi, self.Lv)
-                    src, raw = w["XA"], X[:Mv]              # ln_1 reads the adapter output and moves it back into X
-                    pend[tower] = False
-                if xa_stream and tower == "v":
-                    modes.append((tower, r0, r1, False))
-                elif pend[tower]:
-                    modes.append((tower, r0, r1, True))
-                else:
-                    hip.layernorm_stats(src, b["ln1"].g, b["ln1"].b, LNO[r0:r1], r1 - r0, CEN[r0:r1], RST[r0:r1], raw_out=raw,
-                                        mdev=self._md(w, r0, r1))
-                    modes.append((tower, r0, r1, False))
-                pend[tower] = False
-            shared = len(segs) == 2 and vb["w"] is tb["w"]
-            groups = [(segs[0][1], segs[-1][2], modes)] if shared else [(m[1], m[2], [m]) for m in modes]
-            if last_live and not self.opt.last_block_all_queries:
-                assert not any(m[3] for m in modes)       # (the block before the last one does not produce: see below)
-                cg = [(r0, r1, (self.vblk if ms[0][0] == "v" else self.tblk)[i]["w"]) for r0, r1, ms in groups]
-                self._last_block_attention(w, Bi, Bt, cg)
-                self._last_block_tail(w, Bi, Bt, vb, tb, attended=True)
-                continue
-            if shared and not last_live and self.fused_qkv_attn_enabled():
-                self._fused_qkv_attention(w, i, groups[0][0], groups[0][1], groups[0][2], Bi, Bt)
-            else:
-                for r0, r1, ms in groups:
-                    self._fold_proj(w, i, "qkv", r0, r1, ms, QKV, hip.ACT_NONE)
-                if vb is not None:
-                    hip.attention(QKV[:Mv], AO[:Mv], Bi, self.Lv, self.heads, False)
-                if tb is not None:
-                    self._attention_text(w, QKV, AO, Bt)
-            if last_live:
-                self._last_block_tail(w, Bi, Bt, vb, tb)
-                continue
-            # --- out_proj produces ln_2's operands; c_fc consumes them; c_proj produces the next block's ln_1 operands unless
-            #     that block takes a LayerNorm pass anyway (the compact last block; image rows in front of a lateral adapter
-            #     are produced too -- one launch over both towers -- and overwritten by the adapter's pass)
-            nxt_fold = i + 1 <= n_last and not (i + 1 == n_last and compact and not self.opt.last_block_all_queries)
-            for r0, r1, ms in groups:
-                bw = (self.vblk if ms[0][0] == "v" else self.tblk)[i]["w"]
-                md = self._md(w, r0, r1)
-                if self.fp8:
-                    # out_proj plain (bf16), ln_2 as the e4m3 LayerNorm pass, MLP on the fp8 MFMA; a calibrated c_proj over whole
-                    # tiles produces the next block's ln_1 operands like the bf16 one
-                    hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=X[r0:r1], resid_kind=hip.RESID_F32, mdev=md)
-                    segs2 = [(m[1], m[2], (self.vblk if m[0] == "v" else self.tblk)[i]) for m in ms]
-                    self._ln_f8(w, segs2, "ln2")
-                    prod = nxt_fold and bw.hid_scale is not None and self._calib is None
-                    self._mlp_f8(w, r0, r1, bw, fold_out=hip.FoldOut(LNO[r0:r1], CEN[r0:r1], PART[r0:r1]) if prod else None)
-                    if prod:
-                        hip.rowstat_finalize(PART[r0:r1], CEN[r0:r1], RST[r0:r1], r1 - r0, D, mdev=md)
-                        for m in ms:
-                            pend[m[0]] = True
-                    continue
-                fo = hip.FoldOut(LNO[r0:r1], CEN[r0:r1], PART[r0:r1])
-                res = X[r0:r1]
-                if xa_stream and ms[0][0] == "v":           # (image rows come first: r0 == 0)
-                    res = w["XA"]
-                    if r1 > Mv:
-                        fo = hip.FoldOut(LNO[r0:r1], CEN[r0:r1], PART[r0:r1], resid2=X[r0:r1], split=Mv)
-                hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=res, resid_kind=hip.RESID_F32, fold_out=fo, mdev=md)
-                hip.rowstat_finalize(PART[r0:r1], CEN[r0:r1], RST[r0:r1], r1 - r0, D, mdev=md)
-                self._fold_proj(w, i, "fc", r0, r1, [(m[0], m[1], m[2], True) for m in ms], HID, hip.ACT_QUICKGELU)
-                if nxt_fold:
-                    hip.gemm(HID[r0:r1], bw.wpr, X[r0:r1], bias=bw.bpr, resid=X[r0:r1], resid_kind=hip.RESID_F32,
-                             fold_out=hip.FoldOut(LNO[r0:r1], CEN[r0:r1], PART[r0:r1]), mdev=md)
-                    hip.rowstat_finalize(PART[r0:r1], CEN[r0:r1], RST[r0:r1], r1 - r0, D, mdev=md)
-                    for m in ms:
-                        pend[m[0]] = True
-                else:
-                    hip.gemm(HID[r0:r1], bw.wpr, X[r0:r1], bias=bw.bpr, resid=X[r0:r1], resid_kind=hip.RESID_F32, mdev=md)
-            if taps is not None:
-                if vb is not None:
-                    self._tap_tokens(taps, f"vblock{i}", X[:Mv], Bi, self.Lv)
-                if tb is not None:
-                    self._tap_text(taps, f"tblock{i}", X[Mv:M], w, Bt)
-
-    def _blocks(self, w, Bi, Bt, taps=None, conv_events=None, compact=False, layers=None):
-        if self._fold_eligible(w, Bi, Bt):
-            return self._blocks_fold(w, Bi, Bt, taps, conv_events, compact, layers)
-        Mv, M = w["Mv"], w["M"]
-        X, LNO, QKV, AO, HID = w["X"], w["LNO"], w["QKV"], w["AO"], w["HID"]
-        for i in (range(self.n_layers) if layers is None else layers):
-            vb = self.vblk[i] if Bi else None
-            tb = self.tblk[i] if Bt else None
-            if vb is None and tb is None:
-                continue
-            segs = []                      # (row0, row1, block dict)
-            if vb is not None:
-                segs.append((0, Mv, vb))
-            if tb is not None:
-                segs.append((Mv, M, tb))
-            # --- lateral adapter in front of this vision block
-            vis_src = X[:Mv] if vb is not None else None
-            raw = None
+            src = raw = None
+            by_adapter = False
             if vb is not None and i in self.lateral:
-                j = self.lateral.index(i)
-                if conv_events is not None:
-                    self._wait(torch.cuda.current_stream(self.dev), conv_events[j])
-                    self._adapter(j, w, Bi, t=w["Ts"][j])
-                else:
-                    self._parallel_stage(j, w, Bi)
-                    self._adapter(j, w, Bi)
-                if taps is not None:
-                    if j:
-                        c3 = self.par_specs[j][3]
-                        self._tap_nhwc(taps, f"parallel{j}", w["par"][j], Bi, c3.h_out, c3.cout)
-                    self._tap_tokens(taps, f"adapter{j}", w["XA"], Bi, self.Lv)
-                vis_src, raw = w["XA"], X[:Mv]          # ln_1 reads the adapter output and moves it back into X
-            # --- ln_1 (modality specific parameters; one launch over both towers' rows unless the adapter output
-            #     has to be picked up from its own buffer)
+                # folded: the adapter applies ln_1 itself (rows in registers; the image rows' fp32 stream then sits in XA until
+                # out_proj moves it back to X) unless this block's out_proj is not the producing kernel
+                by_adapter = fold and not last_live and not self.fp8 and not self.opt.adapter_ln1_pass
+                src, raw = self._lateral(w, i, Bi, taps, conv_events, ln1=vb["ln1"] if by_adapter else None)
+            segs = ([self.Seg("v", fold and pend["v"], 0, Mv, vb)] if vb is not None else []) + \
+                   ([self.Seg("t", fold and pend["t"], Mv, M, tb)] if tb is not None else [])
+            self._ln_1(w, fold, segs, src, raw, by_adapter)
+            # --- projections: one launch over both towers' rows when the tensors are shared
+            groups = [(r0, r1, bw, [s for s in segs if r0 <= s.r0 < r1]) for r0, r1, bw in self._groups(segs)]
             f8_qkv = self.fp8_qkv
-            if f8_qkv:
-                if raw is not None:                          # the adapter's output moves back into the residual matrix first
-                    hip.gather_rows(vis_src, raw, Mv)
-                self._ln_f8(w, segs, "ln1")
-            elif len(segs) == 2 and raw is None:
-                hip.layernorm_split(X[:M], vb["ln1"].g, vb["ln1"].b, tb["ln1"].g, tb["ln1"].b, Mv, LNO[:M], M)
-            else:
-                for r0, r1, b in segs:
-                    if b is vb:
-                        hip.layernorm(vis_src, b["ln1"].g, b["ln1"].b, LNO[r0:r1], r1 - r0, raw_out=raw)
-                    else:
-                        hip.layernorm(X[r0:r1], b["ln1"].g, b["ln1"].b, LNO[r0:r1], r1 - r0)
-            # --- projections: one launch over both towers when the tensors are shared
-            groups = [(segs[0][0], segs[-1][1], segs[0][2]["w"])] if len(segs) == 2 and vb["w"] is tb["w"] else \
-                     [(r0, r1, b["w"]) for r0, r1, b in segs]
-            last_live = i == self.n_layers - 1 and compact
             if last_live and not f8_qkv and not self.opt.last_block_all_queries:
-                self._last_block_attention(w, Bi, Bt, groups)
+                assert not any(s.folded for s in segs)    # (the block before the last one does not produce: see below)
+                self._last_block_attention(w, Bi, Bt, segs)
                 self._last_block_tail(w, Bi, Bt, vb, tb, attended=True)
                 continue
-            if (len(groups) == 1 and len(segs) == 2 and not last_live and not f8_qkv and self.fused_qkv_attn_enabled()):
-                # opt-in: in_proj + attention of both towers' rows in one kernel (plain weights: LNO holds the LayerNorm outputs)
-                self._fused_qkv_attention(w, i, 0, M, [("v", 0, Mv, False)], Bi, Bt)
+            if len(groups) < len(segs) and not last_live and not f8_qkv and self.fused_qkv_attn_enabled():
+                # opt-in: in_proj + attention of both towers' rows in one kernel (plain: LNO holds the LayerNorm outputs and no
+                # row statistics exist, the shared packed weights serve all rows)
+                self._fused_qkv_attention(w, i, 0, M, segs if fold else segs[:1], Bi, Bt)
             else:
-                for r0, r1, bw in groups:
+                for r0, r1, bw, ms in groups:
                     if f8_qkv:
                         hip.gemm_f8(w["LNQ"][r0:r1], bw.wqkv_q, QKV[r0:r1], w["RS"][r0:r1], bw.wqkv_s, bias=bw.bqkv)
                     else:
-                        hip.gemm(LNO[r0:r1], bw.wqkv, QKV[r0:r1], bias=bw.bqkv)
+                        self._fold_proj(w, i, "qkv", r0, r1, ms, QKV, hip.ACT_NONE)
                 if vb is not None:
                     hip.attention(QKV[:Mv], AO[:Mv], Bi, self.Lv, self.heads, False)
                 if tb is not None:
@@ -1241,21 +1233,15 @@ class Engine:
             if last_live:
                 self._last_block_tail(w, Bi, Bt, vb, tb)
                 continue
-            for r0, r1, bw in groups:
-                hip.gemm(AO[r0:r1], bw.wo, X[r0:r1], bias=bw.bo, resid=X[r0:r1], resid_kind=hip.RESID_F32)
-            if self.fp8:
-                self._ln_f8(w, segs, "ln2")
-            elif len(segs) == 2:
-                hip.layernorm_split(X[:M], vb["ln2"].g, vb["ln2"].b, tb["ln2"].g, tb["ln2"].b, Mv, LNO[:M], M)
+            if fold:
+                # c_proj produces the next block's ln_1 operands unless that block takes a LayerNorm pass anyway (the compact last
+                # block; image rows in front of a lateral adapter are produced too -- one launch over both towers -- and
+                # overwritten by the adapter's pass)
+                produce = i + 1 <= n_last and not (i + 1 == n_last and compact and not self.opt.last_block_all_queries)
+                for r0, r1, bw, ms in groups:
+                    self._rest_fold(w, i, r0, r1, bw, ms, by_adapter, produce)
             else:
-                for r0, r1, b in segs:
-                    hip.layernorm(X[r0:r1], b["ln2"].g, b["ln2"].b, LNO[r0:r1], r1 - r0)
-            for r0, r1, bw in groups:
-                if self.fp8:
-                    self._mlp_f8(w, r0, r1, bw)
-                else:
-                    hip.gemm(LNO[r0:r1], bw.wfc, HID[r0:r1], bias=bw.bfc, act=hip.ACT_QUICKGELU)
-                    hip.gemm(HID[r0:r1], bw.wpr, X[r0:r1], bias=bw.bpr, resid=X[r0:r1], resid_kind=hip.RESID_F32)
+                self._rest_plain(w, segs, groups)
             if taps is not None:
                 if vb is not None:
                     self._tap_tokens(taps, f"vblock{i}", X[:Mv], Bi, self.Lv)

@@ -303,13 +303,8 @@ class TrainStep:
                 compact = (i == e.n_layers - 1 and len(segs) == 2 and L["adapter"] is None and options.TRAIN.compact_last_block)
                 XM = None if compact else (torch.empty(M, D, dtype=F32, device=e.dev) if fresh else Xc)
                 lno1 = torch.empty(M, D, dtype=BF, device=e.dev)
-                if len(segs) == 2:                          # both towers' rows in one launch (modality-specific gamma / beta per row segment)
-                    hip.layernorm_split(Xc[:M], vb["ln1"].g, vb["ln1"].b, tb["ln1"].g, tb["ln1"].b, Mv, lno1[:M], M)
-                else:
-                    for r0, r1, b in segs:
-                        hip.layernorm(Xc[r0:r1], b["ln1"].g, b["ln1"].b, lno1[r0:r1], r1 - r0)
-                groups = [(r_lo, M, segs[0][2]["w"])] if len(segs) == 2 and vb["w"] is tb["w"] else \
-                         [(r0, r1, b["w"]) for r0, r1, b in segs]
+                e._layernorm(segs, "ln1", Xc, lno1)        # (both towers' rows in one launch, modality-specific gamma / beta)
+                groups = e._groups(segs)
                 qkv = torch.empty(M, 3 * D, dtype=BF, device=e.dev)
                 ao = torch.empty(M, D, dtype=BF, device=e.dev)
                 for r0, r1, bw in groups:
@@ -323,7 +318,8 @@ class TrainStep:
                     xin_c, ao_c = torch.empty(nc, D, dtype=F32, device=e.dev), torch.empty(nc, D, dtype=BF, device=e.dev)
                     hip.gather_rows(Xc, xin_c, nc, row_idx=crow)
                     hip.gather_rows(ao, ao_c, nc, row_idx=crow)
-                    cgroups = [(0, nc, vb["w"])] if vb["w"] is tb["w"] else [(0, Bi, vb["w"]), (Bi, nc, tb["w"])]
+                    csegs = e._live_segs(Bi, Bt, vb, tb)
+                    cgroups = e._groups(csegs)
                     xm_c = torch.empty(nc, D, dtype=F32, device=e.dev)
                     # the compact rows' scales: the table gathered with the same row list as the activations ([2, nc]; a few KB)
                     rs_c = None if rs_a is None else torch.stack([rs_a, rs_m]).index_select(1, crow.long()).contiguous()
@@ -334,7 +330,7 @@ class TrainStep:
                         hip.gemm(ao_c[r0:r1], bw.wo, xm_c[r0:r1], bias=bw.bo, resid=xin_c[r0:r1], resid_kind=hip.RESID_F32,
                                  row_scale=rsc_rows(0, r0, r1))
                     lno2_c = torch.empty(nc, D, dtype=BF, device=e.dev)
-                    hip.layernorm_split(xm_c, vb["ln2"].g, vb["ln2"].b, tb["ln2"].g, tb["ln2"].b, Bi, lno2_c, nc)
+                    e._layernorm(csegs, "ln2", xm_c, lno2_c)
                     h_c, hid_c = torch.empty(nc, 4 * D, dtype=BF, device=e.dev), torch.empty(nc, 4 * D, dtype=BF, device=e.dev)
                     xn_c = torch.empty(nc, D, dtype=F32, device=e.dev)
                     for r0, r1, bw in cgroups:
@@ -354,11 +350,7 @@ class TrainStep:
                 L["x_mid"] = XM if fresh else XM[r_lo:M].clone()
                 XN = torch.empty(M, D, dtype=F32, device=e.dev) if fresh else Xc
                 lno2 = torch.empty(M, D, dtype=BF, device=e.dev)
-                if len(segs) == 2:
-                    hip.layernorm_split(XM[:M], vb["ln2"].g, vb["ln2"].b, tb["ln2"].g, tb["ln2"].b, Mv, lno2[:M], M)
-                else:
-                    for r0, r1, b in segs:
-                        hip.layernorm(XM[r0:r1], b["ln2"].g, b["ln2"].b, lno2[r0:r1], r1 - r0)
+                e._layernorm(segs, "ln2", XM, lno2)
                 h = torch.empty(M, 4 * D, dtype=BF, device=e.dev)
                 hid = torch.empty(M, 4 * D, dtype=BF, device=e.dev)
                 for r0, r1, bw in groups:

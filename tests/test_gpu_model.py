@@ -912,7 +912,7 @@ def test_fp8_mlp_of_one_block_against_the_recipe_emulation(gpu_device, name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# round 4: the LayerNorm fold (engine._blocks_fold)
+# round 4: the LayerNorm fold (engine._blocks with _fold_eligible true)
 # ---------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name,B", [("b32-yfcc-msclips", 256), ("b16-yfcc-msclips", 256)])
