@@ -240,13 +240,17 @@ class TrainStep:
                     w["Ts"] = [torch.empty(Bi * g2, D, dtype=F32, device=e.dev) for _ in e.adapters]
                 side = C.side_stream(e.dev)
                 conv_events = []
-                with hip.forked(side):
+                mine = set(cb.saved)
+                with hip.forked(side) as cur_s:
                     for j in range(len(e.adapters)):
                         cb.stage(j)
                         cb.adapter_top(j, w["Ts"][j])
                         ev = torch.cuda.Event()
                         ev.record(side)
                         conv_events.append(ev)
+                # the raw maps and statistics made there come from the side stream's pool; the backward and the running-statistics
+                # update read them on this stream (behind conv_events), which the allocator has to know before they are freed
+                cb.record_stream(cur_s, skip=mine)
             M = sv["M"] = w["M"]
             sv.update(Lmax=w["Lmax"], pad=w["pad"], Mt_live=w["Mt_live"])
             # stochastic depth: the row-scale tables of every vision block's two branches, [blocks, 2, M] fp32 (image rows 0 or

@@ -683,6 +683,22 @@ class ConvSideBatchNorm:
         self.saved[p] = (graw, mean, rstd, gam, Bi * g * g)
         self.stats[p] = (mean, var, Bi * g * g)
 
+    def record_stream(self, stream, skip=()):
+        """Tell the caching allocator that `stream` reads what the forward saved for the backward (self.saved) and for the running
+        statistics (self.stats) under every BatchNorm prefix not in `skip`: for maps and vectors allocated while another stream
+        was current (TrainStep.forward runs the parallel branch on the conv side stream).  Once per storage: the five vectors of a
+        BatchNorm are rows of one buffer, and the statistics are the saved ones."""
+        told = set()
+        for table in (self.saved, self.stats):
+            for prefix, entry in table.items():
+                if prefix not in skip:
+                    for t in entry:
+                        if isinstance(t, torch.Tensor) and t.is_cuda:
+                            key = t.untyped_storage().data_ptr()
+                            if key not in told:
+                                told.add(key)
+                                t.record_stream(stream)
+
     def update_running_stats(self):
         """running = (1 - m) running + m batch (unbiased variance), num_batches_tracked += 1: in place on the module's buffers."""
         bufs = dict(self.e.model.named_buffers())
