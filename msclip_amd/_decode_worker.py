@@ -28,6 +28,22 @@ def load_pixels(path, size=224):
     return np.array(img.crop((left, top, left + size, top + size)), dtype=np.uint8)
 
 
+def load_source(path, max_side=512):
+    """Image file -> uint8 [h, w, 3] with max(h, w) <= max_side, for the training input path (msclip_amd/pairs.py): decode only,
+    no filter resize on the host -- the crop is cut and resampled on the device (include/msclip_input.h).  JPEG draft mode takes the
+    coarse power-of-two downscale inside the decoder (the largest that keeps both sides >= max_side; a no-op for other formats);
+    whatever is still too large is reduced by the smallest integer factor that fits (Image.reduce: a box average)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        im.draft("RGB", (max_side, max_side))
+        img = im.convert("RGB")
+    w, h = img.size
+    k = -(-max(w, h) // max_side)                        # ceil: the smallest k with ceil(side / k) <= max_side
+    if k > 1:
+        img = img.reduce(k)
+    return np.array(img, dtype=np.uint8)
+
+
 def main(argv):
     from multiprocessing import resource_tracker, shared_memory
     name, depth, batch, size = argv[0], int(argv[1]), int(argv[2]), int(argv[3])
