@@ -44,7 +44,14 @@ extern "C" {
  *   resid_kind 5 (mode 1, generic / streaming kernels): v = resid[store row][n] > 0 ? v : 0 with resid bf16 -- ReLU backward on the
  *   saved activation, which is laid out like the output (same row scatter, ldr); the conv side's input gradients.
  *   resid_kind 6 (bf16 out, generic / streaming kernels): v += resid[store row][n] (bf16) -- a scattered launch accumulating into
- *   an existing map (resid == out: in place); the stride-2 shortcuts' input gradients into their block's main-path gradient. */
+ *   an existing map (resid == out: in place); the stride-2 shortcuts' input gradients into their block's main-path gradient.
+ *   Both are applied AFTER act 2 in the contract's order; for kind 5 the order does not matter (mask and ReLU commute), kind 6 is
+ *   not combined with act 2 (EINVAL: the kernels would clamp the sum).  Both need ldr % 4 == 0.
+ *   Rejected for every kernel (EINVAL, msclip_gemm_variant "invalid"): resid_kind != 0 with resid NULL, act outside 0..2,
+ *   ldo < N (except bn_mode 1, which stores nothing), mode 1 with H, Wd, Cin, Ho, Wo or stride <= 0.
+ *   A tile request the asked-for kernel does not carry in this form is not an error where another kernel does: tile 5 falls back
+ *   to the 128 x 128 kernels (table residual; row scatter with a residual of kind 1 / 2), tile 4 in mode 1 to "conv128"
+ *   (table residual, row scatter); msclip_gemm_variant names the kernel that runs. */
 typedef struct msclip_gemm_desc {
   const void* X;
   const void* W;
@@ -64,8 +71,8 @@ typedef struct msclip_gemm_desc {
   int rpg, radd, roff;   /* rpg > 0; use rpg = INT_MAX, radd = roff = 0 for the identity */
   void* out2;            /* optional second bf16 output: the epilogue value before the activation (NULL: none) */
   float out_scale;       /* out_kind 2 (e4m3 output, msclip_gemm_f8 only): stored value = fp8(epilogue value * out_scale), saturating */
-  int tile;              /* 0 = auto, 1 = 128x128 (4 waves), 4 = 256x256 ping-pong (what auto picks for large problems; dense X, or implicit conv with Cin % 64 == 0), 5 = streaming kernel with LDS-resident weights (K <= 192, or the 3x3 convolutions with 48 input channels; M >= 4096; auto picks it there), 6 = 256x192 two-buffer (implicit conv with N % 192 == 0; on dense operands: the main loop a fused in_proj + attention kernel would run, kept for its calibration -- tools/probes/fused_calib.py), (7 and 8, the two epilogue-hiding kernels of rounds 2-3, were measured slower and retired in round 4: EINVAL) */
-  int wg_cap;            /* 0 = the launch may take every CU; > 0: at most this many persistent workgroups (CUs) for the dense / implicit-conv MFMA kernels (round-4 probe of two half-batch chains on two streams, tools/probes/two_chain_probe.py: measured neutral, the engine leaves it 0) */
+  int tile;              /* 0 = auto, 1 = 128x128 (4 waves), 4 = 256x256 ping-pong (what auto picks for large problems; dense X, or implicit conv with Cin % 64 == 0), 5 = streaming kernel with LDS-resident weights (K <= 192, or the 3x3 convolutions with 48 input channels; M >= 4096; auto picks it there), 6 = 256x192 two-buffer (implicit conv: any N when asked for, auto picks it for N % 192 == 0; on dense operands: the main loop a fused in_proj + attention kernel would run, kept for its calibration -- tools/probes/fused_calib.py), (7 and 8, the two epilogue-hiding kernels of rounds 2-3, were measured slower and retired in round 4: EINVAL) */
+  int wg_cap;            /* 0 = the launch may take every CU; > 0: at most this many persistent workgroups (CUs) for the dense / implicit-conv MFMA kernels (round-4 probe of two half-batch chains on two streams, tools/probes/two_chain_probe.py: measured neutral, the engine leaves it 0; since the probe no kernel reads it: the grids are what they are with 0, and only the small-M kernel behind "dense128" declines a launch that sets it) */
   /* ---- LayerNorm fold (dense ping-pong kernel only; M, seg_split and N multiples of 256; DESIGN.md "LayerNorm fold").
    * Consumer (a projection that follows a LayerNorm, M.py:1027-1028 + 204-219): X holds bf16 (x - center[m]) instead of the
    * LayerNorm output, W carries gamma (W'[n][k] = gamma[k] W[n][k]), and
@@ -127,7 +134,9 @@ int msclip_gemm_splitk_tn(const msclip_gemm_desc* desc, int slices, void* stream
  * per-row scales of X and W: out = epilogue(alpha * row_scale[m] * col_scale[n] * sum_k X[m, k] W[n, k]), same bias /
  * activation / residual / output kinds as msclip_gemm, plus out_kind 2: an e4m3 output scaled by desc->out_scale (no residual;
  * M % 256 == 0, N and ldo multiples of 16) -- c_fc writes the MLP hidden matrix as the fp8 operand of c_proj with one static,
- * calibrated scale per tensor.  Replaces F.linear (M.py:612, 794, 798) when MODEL.SPEC.PRECISION is fp8. */
+ * calibrated scale per tensor.  Replaces F.linear (M.py:612, 794, 798) when MODEL.SPEC.PRECISION is fp8.
+ * "Same kinds": act 0..2, resid_kind 0..2, bf16 / fp32 out, any N / ldo / ldr (tail path), no row scatter (rpg = INT_MAX), tile 0
+ * or 4, no bn_mode, `part` only with xb (the producer form); the descriptor checks every kernel shares apply. */
 int msclip_gemm_f8(const msclip_gemm_desc* desc, const float* row_scale, const float* col_scale, void* stream);
 
 /* LayerNorm (M.py:204-219; parameters (gamma, beta) for rows < split, (gamma2, beta2) from there on) straight to e4m3 with one

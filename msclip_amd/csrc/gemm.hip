@@ -881,8 +881,24 @@ static int device_cus() { return msclip_device_cus(); }
 enum GemmVariant { GV_INVALID = 0, GV_STREAM, GV_PP, GV_DENSE128, GV_PPCONV, GV_CONV192, GV_CONV128, GV_DENSE192 };
 static const char* const kVariantName[] = {"invalid", "stream", "pp", "dense128", "ppconv", "conv192", "conv128", "dense192"};
 
+// What every entry point asks of a descriptor before anything else looks at it (pick_variant, msclip_gemm_f8): a residual kind
+// comes with its pointer (every epilogue dereferences it unguarded), the activation is one the epilogues know (another value
+// would compute none, and on the ping-pong kernel also change the epilogue family), output rows do not overlap (bn_mode 1 stores
+// nothing), and the implicit-conv geometry is positive before anybody divides by it.
+static bool desc_ok(const msclip_gemm_desc* d) {
+  if (!d) return false;
+  if (d->resid_kind != 0 && !d->resid) return false;
+  if (d->act < 0 || d->act > 2) return false;
+  if (d->bn_mode != 1 && d->ldo < d->N) return false;
+  if (d->mode == 1 && (d->H <= 0 || d->Wd <= 0 || d->Cin <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->stride <= 0 ||
+                       (long long)d->Ho * d->Wo > 0x7fffffffll))
+    return false;
+  return true;
+}
+
 static GemmVariant pick_variant(const msclip_gemm_desc* d) {
-  if (!d || !d->X || !d->W || !d->out || !d->zero) return GV_INVALID;
+  if (!desc_ok(d)) return GV_INVALID;
+  if (!d->X || !d->W || !d->out || !d->zero) return GV_INVALID;
   if (d->M <= 0 || d->N <= 0 || d->K <= 0 || (d->K % BK)) return GV_INVALID;
   if (d->mode == 0 && (d->ldx % 8)) return GV_INVALID;
   if (d->ldw < d->K || (d->ldw % 8)) return GV_INVALID;
@@ -891,7 +907,9 @@ static GemmVariant pick_variant(const msclip_gemm_desc* d) {
   if (d->rpg <= 0) return GV_INVALID;
   if (d->resid_kind < 0 || d->resid_kind > 6 || d->out_kind < 0 || d->out_kind > 1) return GV_INVALID;   // (e4m3 outputs: msclip_gemm_f8)
   // resid_kind 6 (+ the bf16 value at the store row: a scattered launch accumulating into an existing map): generic / streaming kernels
-  if (d->resid_kind == 6 && (!d->resid || (d->ldr & 3) || d->tile == 4 || d->out2 || d->rowstat || d->W2 || d->xb || d->out_kind != 0))
+  // (no ReLU: every epilogue adds first and clamps the sum, the contract's order is ReLU, then accumulate; nothing launches the pair)
+  if (d->resid_kind == 6 && (!d->resid || (d->ldr & 3) || d->tile == 4 || d->out2 || d->rowstat || d->W2 || d->xb || d->out_kind != 0 ||
+                             d->act == 2))
     return GV_INVALID;
   // resid_kind 5 (ReLU mask at the store row; the conv side's input gradients): implicit-conv launches of the generic / streaming
   // kernels only
@@ -1006,7 +1024,10 @@ extern "C" int msclip_gemm_splitk_tn(const msclip_gemm_desc* d, int slices, void
 // activation / residual epilogues.  Dense operands only.
 extern "C" int msclip_gemm_f8(const msclip_gemm_desc* d, const float* row_scale, const float* col_scale, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_gemm_f8, stream, d, row_scale, col_scale);
-  if (!d || !d->X || !d->W || !d->out || !d->zero || !row_scale || !col_scale) return MSCLIP_EINVAL;
+  if (!desc_ok(d) || !d->X || !d->W || !d->out || !d->zero || !row_scale || !col_scale) return MSCLIP_EINVAL;
+  // what this entry does not carry: the BatchNorm passes (streaming kernel), column-sum partials (resid_kind 4 of msclip_gemm;
+  // `part` here belongs to the producer form, with xb), any kernel but the ping-pong one
+  if (d->bn_mode || (d->part && !d->xb) || (d->tile != 0 && d->tile != 4)) return MSCLIP_EINVAL;
   if (d->mode != 0 || d->M <= 0 || d->N <= 0 || d->K <= 0 || (d->K % 128) || (d->ldx % 16) || (d->ldw % 16) || d->ldx < d->K ||
       d->ldw < d->K || d->rpg != 0x7fffffff || d->out2 || d->out_kind < 0 || d->out_kind > 2 || d->resid_kind < 0 || d->resid_kind > 2 ||
       d->rowstat || d->W2)

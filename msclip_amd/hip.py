@@ -550,8 +550,10 @@ _WG_CAP = [0]
 
 
 def set_wg_cap(n):
-    """Upper bound on the persistent workgroups (= CUs) a msclip_gemm / msclip_gemm_f8 launch may take (0: all of them); returns
-    the previous value.  The engine's two-chain schedule sets it around each chain so that the other chain's kernels find CUs."""
+    """msclip_gemm_desc.wg_cap of the launches that follow (0: none); returns the previous value.  It was the upper bound on a
+    launch's persistent workgroups in the two-chain probe (tools/probes/two_chain_probe.py: measured neutral); no kernel reads it
+    any more -- the grids are what they are with 0 -- and the engine never sets it.  Its one effect today: the small-M kernel
+    behind "dense128" declines a launch that carries one (include/msclip_hip.h)."""
     prev = _WG_CAP[0]
     _WG_CAP[0] = int(n)
     return prev
@@ -589,6 +591,8 @@ def gemm(x, w, out, *, M=None, bias=None, resid=None, resid_kind=0, act=0, alpha
     row_scale (fp32 [>= M], msclip_gemm_rowscale; needs resid_kind RESID_F32, an fp32 out, no activation):
     out = resid + row_scale[m] * (alpha * x @ w^T + bias) -- the residual branch behind a DropPath; None: plain msclip_gemm."""
     _bf16(w)
+    if resid_kind != RESID_NONE and resid is None:     # refused here, before the library is entered (which refuses it as well)
+        raise HipError(f"msclip_gemm: resid_kind {resid_kind} without a resid tensor")
     d = GemmDesc()
     d.X, d.W, d.zero, d.out = x.data_ptr(), w.data_ptr(), zero_page(x.device).data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
@@ -709,6 +713,8 @@ def gemm_f8(xq, wq, out, row_scale, col_scale, *, M=None, bias=None, resid=None,
     assert xq.dtype == torch.uint8 and wq.dtype == torch.uint8 and xq.stride(-1) == 1 and wq.stride(-1) == 1
     _f32(col_scale)
     assert row_scale.dtype == torch.float32
+    if resid_kind != RESID_NONE and resid is None:
+        raise HipError(f"msclip_gemm_f8: resid_kind {resid_kind} without a resid tensor")
     d = GemmDesc()
     d.X, d.W, d.zero, d.out = xq.data_ptr(), wq.data_ptr(), zero_page(xq.device).data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
