@@ -8,15 +8,17 @@ integer `reduce`, no filter resize), and one task per batch tokenizes its captio
 header holds the batch's token ids, image sizes, crop boxes and flip flags, so that a batch is ONE host-to-device copy on a copy
 stream.  The random-resized crop, the flip and the normalisation are one launch on the device (input_hip.resized_crop).  The boxes
 are computed on the host (augment.random_resized_crop_boxes) from uniforms of a CPU generator the pipeline owns, once the workers
-have reported the sizes: nothing is read back from the device.  img and tok are device tensors; index (int64 [B], the batch's
-positions in `items`) stays on the host, where the order was made.
+have reported the sizes: nothing is read back from the device.  Where the settings turn a colour stage on (AUG.COLOR_JITTER,
+AUG.GRAY_SCALE, AUG.GAUSSIAN_BLUR: augment.aug_settings(config, colour=True)), the per-image records of augment.colour_params travel
+in the same header and color_hip.color_augment runs on resized_crop's uint8 result, on the same stream.  img and tok are device
+tensors; index (int64 [B], the batch's positions in `items`) stays on the host, where the order was made.
 """
 import concurrent.futures as cf
 import os
 
 import torch
 
-from . import augment, input_hip
+from . import augment, color_hip, input_hip
 from ._decode_worker import load_source
 from .zeroshot import effective_cores, normalise_lut
 
@@ -47,7 +49,7 @@ class PairPipeline:
     """settings: augment.aug_settings(config).  `slot`: the side of a staging slot = the largest side a decoded image keeps
     (load_source's max_side); at most MSCLIP_CROP_MAX_SCALE times the training size.  rank / world: this process's share of every
     epoch (augment.epoch_order); an epoch is whole batches only.  After a batch has been yielded, last_dims / last_boxes /
-    last_flip are host tensors that describe it."""
+    last_flip are host tensors that describe it, and with a colour stage on so are last_ops / last_coef (augment.colour_params)."""
 
     def __init__(self, items, batch_size, device, settings, tokenizer=None, seed=0, workers=None, depth=3, slot=512, rank=0, world=1):
         self.items, self.bs, self.dev = list(items), int(batch_size), torch.device(device)
@@ -63,11 +65,16 @@ class PairPipeline:
         self.depth = max(2, int(depth))
         self.pool = cf.ThreadPoolExecutor(self.workers)
         B, S = self.bs, self.slot
-        # one staging buffer: tokens int64 [B, 77] | dims int32 [B, 2] | boxes int32 [B, 4] | flip int32 [B] | pad | pixels [B, S, S, 3]
+        # the colour stages that are on (msclip_color_augment's mask); 0: the pipeline draws, stages and launches what it did without
+        self.stages = augment.colour_stages(self.settings)
+        # one staging buffer: tokens int64 [B, 77] | dims int32 [B, 2] | boxes int32 [B, 4] | flip int32 [B] | with a colour stage
+        # on: ops int32 [B, 8] | coef fp32 [B, 12] | pad | pixels [B, S, S, 3]
         self.o_dims = B * CONTEXT * 8
         self.o_boxes = self.o_dims + B * 8
         self.o_flip = self.o_boxes + B * 16
-        self.o_pix = _up(self.o_flip + B * 4, 256)
+        self.o_ops = self.o_flip + B * 4
+        self.o_coef = self.o_ops + (B * 4 * color_hip.OPS if self.stages else 0)
+        self.o_pix = _up(self.o_coef + (B * 4 * color_hip.COEF if self.stages else 0), 256)
         nbytes = self.o_pix + B * S * S * 3
         self.pin = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
         self.gpu = [torch.empty(nbytes, dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
@@ -81,15 +88,19 @@ class PairPipeline:
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.lut = normalise_lut(settings["mean"], settings["std"]).to(self.dev).contiguous()
         self.gen = torch.Generator()
-        self.last_dims = self.last_boxes = self.last_flip = None
+        self.last_dims = self.last_boxes = self.last_flip = self.last_ops = self.last_coef = None
         self.epoch = self.pos = 0
         self.set_epoch(0)
 
     def _views(self, t):
         B, S = self.bs, self.slot
-        return dict(tok=t[:self.o_dims].view(torch.int64).view(B, CONTEXT), dims=t[self.o_dims:self.o_boxes].view(torch.int32).view(B, 2),
-                    boxes=t[self.o_boxes:self.o_flip].view(torch.int32).view(B, 4),
-                    flip=t[self.o_flip:self.o_flip + B * 4].view(torch.int32), pix=t[self.o_pix:].view(B, S, S, 3))
+        v = dict(tok=t[:self.o_dims].view(torch.int64).view(B, CONTEXT), dims=t[self.o_dims:self.o_boxes].view(torch.int32).view(B, 2),
+                 boxes=t[self.o_boxes:self.o_flip].view(torch.int32).view(B, 4),
+                 flip=t[self.o_flip:self.o_flip + B * 4].view(torch.int32), pix=t[self.o_pix:].view(B, S, S, 3))
+        if self.stages:
+            v["ops"] = t[self.o_ops:self.o_coef].view(torch.int32).view(B, color_hip.OPS)
+            v["coef"] = t[self.o_coef:self.o_coef + B * 4 * color_hip.COEF].view(torch.float32).view(B, color_hip.COEF)
+        return v
 
     # ---- the epoch, the position in it and the generator: what a resumed pipeline needs
     def set_epoch(self, epoch):
@@ -155,6 +166,12 @@ class PairPipeline:
                 pv["dims"].copy_(sizes.to(torch.int32))
                 pv["boxes"].copy_(boxes)
                 pv["flip"].copy_(flip)
+                ops = coef = None
+                if self.stages:                          # (after the flip uniforms: with every colour stage off, the draws of before)
+                    uc = torch.rand(self.bs, augment.COLOUR_DRAWS, dtype=torch.float64, generator=self.gen)
+                    ops, coef = augment.colour_params(uc, self.settings)
+                    pv["ops"].copy_(ops)
+                    pv["coef"].copy_(coef)
                 cur = torch.cuda.current_stream(self.dev)
                 with torch.cuda.stream(self.copy_stream):
                     self.copy_stream.wait_event(self.free[k])        # gpu[k]'s previous batch has been consumed
@@ -166,11 +183,18 @@ class PairPipeline:
                 if nxt < nb:
                     inflight[nxt] = self._submit(nxt)
                 cur.wait_event(landed)
-                img = input_hip.resized_crop(gv["pix"], gv["dims"], gv["boxes"], self.lut, self.size, flip=gv["flip"],
-                                             filter=self.settings["interpolation"])
+                if self.stages:
+                    # (msclip_resized_crop requires an `out`: its fp32 result is written, then overwritten by the colour stage)
+                    img, u8 = input_hip.resized_crop(gv["pix"], gv["dims"], gv["boxes"], self.lut, self.size, flip=gv["flip"],
+                                                     filter=self.settings["interpolation"], want_u8=True)
+                    color_hip.color_augment(u8, gv["ops"], gv["coef"], self.lut, stages=self.stages, out=img)
+                else:
+                    img = input_hip.resized_crop(gv["pix"], gv["dims"], gv["boxes"], self.lut, self.size, flip=gv["flip"],
+                                                 filter=self.settings["interpolation"])
                 tok = gv["tok"].clone()
                 self.free[k].record(cur)
                 self.last_dims, self.last_boxes, self.last_flip = sizes.to(torch.int32), boxes, flip
+                self.last_ops, self.last_coef = ops, coef
                 self.pos = b + 1
                 yield img, tok, idx
         finally:

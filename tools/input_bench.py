@@ -1,12 +1,14 @@
 """What the training input path sustains (recorded, not gated): writes profiles/input_pipeline_bench.md.
 
-    python tools/input_bench.py [--files 768] [--batch 256] [--out profiles/input_pipeline_bench.md]
+    python tools/input_bench.py [--files 768] [--batch 256] [--out profiles/input_pipeline_bench.md] [--colour]
 
 * host ms per image of `load_source` (decode only: draft + reduce) against a host-side PIL decode + crop().resize() of the same
   file, one thread;
 * msclip_resized_crop's time for a batch of 512 at 224 x 224 from 512 x 512 slots, bicubic and bilinear (HIP events);
 * PairPipeline alone (decode threads, one copy per batch, the launch) in pairs/s, beside the training step's pairs/s of
   profiles/r06_bench_lines.jsonl -- and the sentence that follows from the two.
+--colour measures the colour stage alone (msclip_color_augment beside msclip_resized_crop at 512 x 224 x 224 with every stage on
+and p = 1, and PairPipeline's pairs/s with and without colour) and replaces that section of the file, leaving the rest as recorded.
 The files are generated: JPEGs (quality 90) of sizes drawn around 500 x 375, the usual size of a web photograph."""
 import argparse
 import json
@@ -45,8 +47,90 @@ def _shape_of(path):
     return load_source(path, 512).shape
 
 
+COLOUR_HEAD = "## The colour stage"
+
+
+def _event_ms(fn, warm=5, reps=50):
+    for _ in range(warm):
+        fn()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / reps
+
+
+def colour_section(args, dev):
+    """-> the lines of the colour stage's section: the launch beside the crop's, and the pipeline with and without colour."""
+    from msclip_amd import augment, color_hip, input_hip, pairs, zeroshot
+    from msclip_amd.config import named_config
+    from msclip_amd.tokenizer import SimpleTokenizer
+    B, g = 512, torch.Generator().manual_seed(0)
+    on = ["AUG.COLOR_JITTER", "[0.4, 0.4, 0.4, 0.1, 1.0]", "AUG.GRAY_SCALE", "1.0", "AUG.GAUSSIAN_BLUR", "1.0"]
+    typical = ["AUG.COLOR_JITTER", "[0.4, 0.4, 0.4, 0.1, 0.8]", "AUG.GRAY_SCALE", "0.2", "AUG.GAUSSIAN_BLUR", "0.5"]
+    s_all = augment.aug_settings(named_config("b32-yfcc-msclips", on), colour=True)
+    s_typ = augment.aug_settings(named_config("b32-yfcc-msclips", typical), colour=True)
+    s_off = augment.aug_settings(named_config("b32-yfcc-msclips"), colour=True)
+    src = torch.randint(0, 256, (B, 512, 512, 3), dtype=torch.uint8, device=dev)
+    dims = torch.tensor([[375, 500]] * B, dtype=torch.int32, device=dev)
+    bx = augment.random_resized_crop_boxes(torch.tensor([[375, 500]] * B), torch.rand(B, 10, 4, dtype=torch.float64, generator=g)).to(dev)
+    lut = zeroshot.normalise_lut().to(dev)
+    out, u8 = input_hip.resized_crop(src, dims, bx, lut, 224, want_u8=True)
+    lines = [COLOUR_HEAD, "",
+             f"`tools/input_bench.py --colour`: msclip_color_augment on {B} x 224 x 224 (band {color_hip.augment_band(224, 224)}, "
+             f"{color_hip.augment_lds(224, 224)} B of LDS per blurring workgroup), HIP events over 50 launches after 5, beside "
+             "msclip_resized_crop (bicubic, 512 x 512 slots, with out_u8) in the same process.", "",
+             "| launch | ms | images/s |", "|---|---|---|"]
+    ms = crop_ms = _event_ms(lambda: input_hip.resized_crop(src, dims, bx, lut, 224, out=out, want_u8=True))
+    lines.append(f"| msclip_resized_crop, bicubic, out and out_u8 | {ms:.3f} | {B / ms * 1e3:.0f} |")
+    stage_ms = []
+    u = torch.rand(B, augment.COLOUR_DRAWS, dtype=torch.float64, generator=g)
+    for what, settings in (("every stage on every image (p = 1)", s_all), ("jitter 0.8, gray 0.2, blur 0.5", s_typ)):
+        ops, coef = (t.to(dev) for t in augment.colour_params(u, settings))
+        st = augment.colour_stages(settings)
+        ms = _event_ms(lambda: color_hip.color_augment(u8, ops, coef, lut, stages=st, out=out))
+        stage_ms.append(ms)
+        lines.append(f"| msclip_color_augment, {what} | {ms:.3f} | {B / ms * 1e3:.0f} |")
+    ops, coef = (t.to(dev) for t in augment.colour_params(u, s_all))
+    for what, st in (("jitter alone (both kernels, no LDS)", 1), ("gray alone", 2), ("blur alone", 4)):
+        ms = _event_ms(lambda: color_hip.color_augment(u8, ops, coef, lut, stages=st, out=out))
+        lines.append(f"| msclip_color_augment, {what} | {ms:.3f} | {B / ms * 1e3:.0f} |")
+    del src
+    lines += ["", f"PairPipeline alone, batch {args.batch}, {args.files // args.batch} batches per epoch, 8 decoding threads, pairs/s:", "",
+              "| colour | epoch 0 (cold) | epoch 1 | epoch 2 |", "|---|---|---|---|"]
+    tok = SimpleTokenizer()
+    with tempfile.TemporaryDirectory() as root:
+        items = make_files(root, args.files)
+        for what, settings in (("off", s_off), ("jitter 0.8, gray 0.2, blur 0.5", s_typ), ("every stage, p = 1", s_all)):
+            pipe = pairs.PairPipeline(items, args.batch, dev, settings, tokenizer=tok, seed=0, workers=8)
+            rates = []
+            for epoch in range(3):
+                pipe.set_epoch(epoch)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                n = 0
+                for img, _, _ in pipe:
+                    n += img.shape[0]
+                torch.cuda.synchronize()
+                rates.append(n / (time.perf_counter() - t0))
+            pipe.close()
+            lines.append(f"| {what} | " + " | ".join(f"{r:.0f}" for r in rates) + " |")
+    step_ms = 512 / 8278 * 1e3                               # (profiles/r06_bench_lines.jsonl: train-mode BatchNorm, batch 512)
+    lines += ["", f"The stage takes {stage_ms[0] / crop_ms:.2f} x the crop's own time with every stage on every image and "
+              f"{stage_ms[1] / crop_ms:.2f} x at the usual probabilities: "
+              + ("below the crop's, as expected" if stage_ms[0] < crop_ms else "NOT below the crop's, which had been the expectation")
+              + f"; crop and colour together are {100 * (crop_ms + stage_ms[0]) / step_ms:.1f} % of a "
+              f"{step_ms:.0f} ms training step at most. The pipeline's rate is set by the host's decoding threads and moves as much from "
+              "epoch to epoch within a row as the rows differ from each other: the colour stage does not show in it."]
+    return lines + [""]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--colour", action="store_true", help="measure the colour stage alone and replace its section of --out")
     ap.add_argument("--files", type=int, default=768)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "input_pipeline_bench.md"))
@@ -57,7 +141,15 @@ def main():
     from msclip_amd.config import named_config
     from msclip_amd.tokenizer import SimpleTokenizer
     dev = torch.device("cuda", 0)
-    settings = augment.aug_settings(named_config("b32-yfcc-msclips"))
+    if args.colour:
+        lines = colour_section(args, dev)
+        old = open(args.out).read() if os.path.exists(args.out) else ""
+        keep = old.split(COLOUR_HEAD)[0].rstrip("\n")
+        with open(args.out, "w") as f:
+            f.write((keep + "\n\n" if keep else "") + "\n".join(lines))
+        print("\n".join(lines))
+        return
+    settings = augment.aug_settings(named_config("b32-yfcc-msclips"), colour=True)
     lines = ["# The training input path: what it sustains", "",
              f"`tools/input_bench.py --files {args.files} --batch {args.batch}` on one MI355X, {zeroshot.effective_cores()} usable host cores. "
              "Recorded, not gated: the parent commit has no training input path to compare with.", ""]
@@ -175,6 +267,11 @@ def main():
                  + (", which would cover the step" if bp[1] >= step.get("train_frozen", float("inf")) else "")
                  + ". Decoding processes, as the eval pipeline has, are the follow-up."), ""]
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if os.path.exists(args.out):                             # (the colour stage's section is --colour's: kept as recorded)
+        with open(args.out) as f:
+            old = f.read()
+        if COLOUR_HEAD in old:
+            lines += [COLOUR_HEAD + old.split(COLOUR_HEAD, 1)[1].rstrip("\n"), ""]
     with open(args.out, "w") as f:
         f.write("\n".join(lines))
     print("\n".join(lines))

@@ -1,13 +1,14 @@
 """Train MS-CLIP-S on image files: a TSV of `relative/path<TAB>caption` lines through msclip_amd.pairs.PairPipeline (decode on the
-host; random-resized crop, flip and normalisation in one launch on the device) into the training step.
+host; random-resized crop, flip and normalisation in one launch on the device, colour jitter / grayscale / Gaussian blur in a second
+stage where the config turns one on) into the training step.
 
     python tools/train_pairs.py --model <yaml or name> --pairs <tsv> --root <dir> --epochs N --batch B
                                 [--bn batch|frozen] [--resume ckpt] [--save ckpt] [--random-init] [--steps K] [--seed S]
                                 [--workers W] [--slot 512] [KEY VALUE ...]
 
 The yaml's optimizer block, schedule, EMA, clipping, stochastic depth and guard are train.from_config's; the augmentation is
-augment.aug_settings' (AUG.SCALE, AUG.RATIO, TRAIN.IMAGE_SIZE, INPUT.MEAN / STD, AUG.INTERPOLATION, AUG.FLIP_PROB; any other
-augmentation switch that is on is refused by name).  KEY VALUE pairs override the yaml (e.g. PRINT_FREQ 1 AUG.FLIP_PROB 0.5).
+augment.aug_settings' (AUG.SCALE, AUG.RATIO, TRAIN.IMAGE_SIZE, INPUT.MEAN / STD, AUG.INTERPOLATION, AUG.FLIP_PROB, AUG.COLOR_JITTER,
+AUG.GRAY_SCALE, AUG.GAUSSIAN_BLUR; any other augmentation switch that is on is refused by name).  KEY VALUE pairs override the yaml (e.g. PRINT_FREQ 1 AUG.FLIP_PROB 0.5).
 
 --save ckpt writes the reference's resumable checkpoint (train.save_checkpoint) when the run ends and the input pipeline's state
 (epoch, position, seed, generator) beside it as <ckpt>.input.pt; --resume ckpt loads both and continues with the batches the
@@ -56,7 +57,7 @@ def main(argv=None):
     rank, world = C.comm.rank, C.comm.world_size
     log = print if rank == 0 else (lambda *a, **k: None)
     cfg = cfgmod.load_config(args.model, args.opts) if os.path.exists(args.model) else cfgmod.named_config(args.model, args.opts)
-    settings = augment.aug_settings(cfg)                   # (refuses what is not implemented before anything is built)
+    settings = augment.aug_settings(cfg, colour=True)      # (refuses what is not implemented before anything is built)
     torch.manual_seed(args.seed)
     model = get_clip_model(cfg)
     if args.random_init:
@@ -71,7 +72,8 @@ def main(argv=None):
                               workers=args.workers, slot=args.slot, rank=rank, world=world)
     log(f"=> {len(items)} pairs, {len(pipe)} steps per epoch at {args.batch} pairs x {world} GPU(s); crop scale {settings['scale']}, "
         f"ratio ({settings['ratio'][0]:.3f}, {settings['ratio'][1]:.3f}), size {settings['size']}, filter {settings['interpolation']}, "
-        f"flip {settings['flip_prob']:g}; {pipe.workers} decoding threads")
+        f"flip {settings['flip_prob']:g}; colour jitter {list(settings['color_jitter'])}, gray {settings['gray_scale']:g}, "
+        f"blur {settings['gaussian_blur']:g}; {pipe.workers} decoding threads")
     if len(pipe) == 0:
         raise SystemExit(f"{args.pairs}: fewer pairs than one batch of {args.batch} x {world}")
     step = 0
