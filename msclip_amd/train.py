@@ -182,75 +182,9 @@ class TrainStep:
         e = self.eng
         e.refresh()
         with torch.cuda.device(e.dev), torch.no_grad():
-            Bi, Bt = img.shape[0], tok.shape[0]
-            assert Bi == Bt, "a training step needs image-text pairs"
-            if drop_masks is not None:
-                drop_masks = self._check_drop_masks(drop_masks, Bi)
-            elif self.drop_path:
-                drop_masks = self.draw_drop_masks(Bi)
-            self.last_drop_masks = drop_masks
-            if e.Lv > hip.ATTENTION_BWD_MAX_L or e.Lt > hip.ATTENTION_BWD_MAX_L:
-                raise NotImplementedError(f"msclip_attention_bwd covers sequences up to {hip.ATTENTION_BWD_MAX_L} tokens")
-            self._release_saved()                                  # a forward that was never differentiated: release its maps
-            w = e._workspace(Bi, Bt)
-            # the conv side's maps (w["stem"], w["par"], w["pool"], S1, P0) -- or the patch-conv model's patch matrix
-            # w["PATCH"] -- are read again by backward(): until then the engine's inference entry points (an eval / logging
-            # call of the same shape in between) get another workspace
-            w["held"] = True
-            # captions run packed like the inference path (engine.text_pack_enabled): rows behind a caption's EOT position
-            # neither influence an output nor receive a gradient.  `tok` may be a batch staged ahead (engine.stage_captions).
-            pack = e.text_pack_enabled()
-            cap = tok if isinstance(tok, Captions) else None
-            tokc = cap.tok if cap is not None else e._check_tok(tok)
-            if pack and cap is None:
-                cap = e.stage_captions(tokc)
-            if not pack:
-                cap = None
-                e._text_unpacked(w, Bt)
-            else:
-                e._text_sizes(cap, w, Bt)                   # the host read (immediate for a batch staged a step ahead)
-            Mv = w["Mv"]
-            D = e.D
-            X = w["X"]
-            sv = dict(Bi=Bi, Bt=Bt, Mv=Mv, layers=[None] * e.n_layers, tok=tokc, w=w, cap=cap)
-            # ---- fronts (the conv side's maps stay in the workspace `w`; the tokens in front of ln_pre are cloned)
-            keep = []
-            sv["img"] = e._check_img(img)
-            cb = None
-            if self.bn == "batch" and not e.patch:             # (the patch-conv model has no BatchNorm: bn is moot there)
-                if self.convbn is None:
-                    self.convbn = ConvSideBatchNorm(self)
-                cb = self.convbn
-                cb.begin(sv["img"], w, Bi)
-                cb.front()
-            # unfused=True at every engine call: the conv side runs layer by layer, every map the backward reads stays in `w`
-            e._vision_front(sv["img"], w, Bi, keep_pre=keep, convs_done=cb is not None, unfused=True)
-            sv["tok_pre"] = keep[0]
-            g2 = e.g * e.g
-            # frozen statistics: the image-only conv branch + the adapters' top-down halves on the engine's side stream, as in
-            # the inference schedule (same-box A/B: 89.6-90.2 -> 88.5-88.9 ms per step)
-            conv_events = None
-            side_ok = not e.patch and gradgemm.lane_enabled() and e.lateral == sorted(e.lateral)
-            if side_ok and cb is None:
-                conv_events = e._conv_branch_on_side_stream(w, Bi, unfused=True)
-            elif side_ok:
-                # train-mode BatchNorm: the same for the raw-conv -> statistics -> normalise chains of the parallel branch and
-                # the adapters' top-down halves (they depend on the image only)
-                if w["Ts"] is None:
-                    w["Ts"] = [torch.empty(Bi * g2, D, dtype=F32, device=e.dev) for _ in e.adapters]
-                side = C.side_stream(e.dev)
-                conv_events = []
-                mine = set(cb.saved)
-                with hip.forked(side) as cur_s:
-                    for j in range(len(e.adapters)):
-                        cb.stage(j)
-                        cb.adapter_top(j, w["Ts"][j])
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        conv_events.append(ev)
-                # the raw maps and statistics made there come from the side stream's pool; the backward and the running-statistics
-                # update read them on this stream (behind conv_events), which the allocator has to know before they are freed
-                cb.record_stream(cur_s, skip=mine)
+            sv = self._begin_forward(img, tok, drop_masks)
+            w, Bi, drop_masks = sv["w"], sv["Bi"], self.last_drop_masks
+            cb, conv_events = self._conv_side_forward(sv)
             M = sv["M"] = w["M"]
             sv.update(Lmax=w["Lmax"], pad=w["pad"], Mt_live=w["Mt_live"])
             # stochastic depth: the row-scale tables of every vision block's two branches, [blocks, 2, M] fp32 (image rows 0 or
@@ -258,178 +192,258 @@ class TrainStep:
             # the slices saved with the layer (None: the option is off and nothing below changes)
             dp_tab = None if drop_masks is None else drop_path_table(drop_masks, Bi, e.Lv, M, self.drop_path_mode, 1.0 - self.drop_path)
             dp_next = 0
-            e._text_front(sv["tok"], w, Bt)
+            e._text_front(sv["tok"], w, sv["Bt"])
             # ---- blocks.  Xc = the residual matrix the next layer reads: the workspace's X at first; every layer that runs over
             # all rows writes its two residual updates into fresh matrices (the backward needs the layer's input and its
             # post-attention state: they stay where they are instead of being cloned), so Xc moves on.
-            Xc = X
+            Xc = w["X"]
             for i in range(e.n_layers):
-                vb = e.vblk[i]
-                tb = e.tblk[i]
                 L = dict(adapter=None, rs=None)
-                if vb is not None and dp_tab is not None:
+                if e.vblk[i] is not None and dp_tab is not None:
                     L["rs"] = (dp_tab[dp_next, 0], dp_tab[dp_next, 1])          # (attention branch, MLP branch), each fp32 [M]
                     dp_next += 1
-                rs_a, rs_m = L["rs"] if L["rs"] is not None else (None, None)
-
-                def rs_rows(t, r0, r1):                    # a launch over rows [r0, r1): its slice of the table (text-only launches: none)
-                    return t[r0:r1] if (t is not None and r0 < Mv) else None
-                if vb is not None and i in e.lateral:
-                    j = e.lateral.index(i)
-                    a = e.adapters[j]
-                    asum = torch.empty(Mv, D, dtype=F32, device=e.dev)
-                    if cb is not None and conv_events is not None:
-                        torch.cuda.current_stream(e.dev).wait_event(conv_events[j])
-                        cb.adapter_sum(j, Xc[:Mv], w["Ts"][j], asum)
-                    elif cb is not None:
-                        cb.stage(j)
-                        cb.adapter_top(j, w["T"])
-                        cb.adapter_sum(j, Xc[:Mv], w["T"], asum)
-                    elif conv_events is not None:
-                        torch.cuda.current_stream(e.dev).wait_event(conv_events[j])
-                        hip.adapter_sum(Xc[:Mv], w["Ts"][j], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
-                    else:
-                        e._parallel_stage(j, w, Bi, unfused=True)
-                        hip.dwpool(w["par"][j], a["pool"], w["pool"][j], Bi, e.par_hw[j], e.par_hw[j], a["C"], a["k"])
-                        hip.gemm(w["pool"][j], a["pw"].weight, w["T"], M=Bi * g2, N=a["pw"].cout, bias=a["pw"].bias, ldx=a["pw"].cin)
-                        hip.adapter_sum(Xc[:Mv], w["T"], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
-                    x_pre = Xc[:Mv].clone()                                                   # what the depthwise 3x3 read
-                    hip.layernorm(asum, a["ln"].g, a["ln"].b, Xc[:Mv], Mv)                    # X[:Mv] <- ln_adapt(sum), fp32
-                    L["adapter"] = dict(j=j, sum=asum, x_pre=x_pre)
-                segs = ([(0, Mv, vb)] if vb is not None else []) + [(Mv, M, tb)]
-                r_lo = segs[0][0]
-                fresh = r_lo == 0                         # (text block 0 leaves the image rows alone: in place, cloned)
-                L["x_in"] = Xc if fresh else Xc[r_lo:M].clone()
-                # Round 6: behind the LAST block only x[:, 0] of every image (M.py:2685) and the EOT row of every caption (M.py:3057-3060)
-                # are read, and out_proj / ln_2 / c_fc / c_proj are row-wise: they run -- forward here, backward in backward() -- on
-                # those Bi + Bt rows instead of on every token (what the inference path has done since round 3; the rows' gradients
-                # are the only non-zero ones behind the block, so every parameter gradient is unchanged)
-                compact = (i == e.n_layers - 1 and len(segs) == 2 and L["adapter"] is None and options.TRAIN.compact_last_block)
-                XM = None if compact else (torch.empty(M, D, dtype=F32, device=e.dev) if fresh else Xc)
-                lno1 = torch.empty(M, D, dtype=BF, device=e.dev)
-                e._layernorm(segs, "ln1", Xc, lno1)        # (both towers' rows in one launch, modality-specific gamma / beta)
-                groups = e._groups(segs)
-                qkv = torch.empty(M, 3 * D, dtype=BF, device=e.dev)
-                ao = torch.empty(M, D, dtype=BF, device=e.dev)
-                for r0, r1, bw in groups:
-                    hip.gemm(lno1[r0:r1], bw.wqkv, qkv[r0:r1], bias=bw.bqkv)
-                if vb is not None:
-                    hip.attention(qkv[:Mv], ao[:Mv], Bi, e.Lv, e.heads, False)
-                e._attention_text(w, qkv, ao, Bt)
-                if compact:
-                    nc = Bi + Bt
-                    crow = torch.cat([torch.arange(0, Mv, e.Lv, dtype=torch.int32, device=e.dev), w["eot"][:Bt]])   # live rows of X
-                    xin_c, ao_c = torch.empty(nc, D, dtype=F32, device=e.dev), torch.empty(nc, D, dtype=BF, device=e.dev)
-                    hip.gather_rows(Xc, xin_c, nc, row_idx=crow)
-                    hip.gather_rows(ao, ao_c, nc, row_idx=crow)
-                    csegs = e._live_segs(Bi, Bt, vb, tb)
-                    cgroups = e._groups(csegs)
-                    xm_c = torch.empty(nc, D, dtype=F32, device=e.dev)
-                    # the compact rows' scales: the table gathered with the same row list as the activations ([2, nc]; a few KB)
-                    rs_c = None if rs_a is None else torch.stack([rs_a, rs_m]).index_select(1, crow.long()).contiguous()
-
-                    def rsc_rows(k, r0, r1):
-                        return rs_c[k, r0:r1] if (rs_c is not None and r0 < Bi) else None
-                    for r0, r1, bw in cgroups:
-                        hip.gemm(ao_c[r0:r1], bw.wo, xm_c[r0:r1], bias=bw.bo, resid=xin_c[r0:r1], resid_kind=hip.RESID_F32,
-                                 row_scale=rsc_rows(0, r0, r1))
-                    lno2_c = torch.empty(nc, D, dtype=BF, device=e.dev)
-                    e._layernorm(csegs, "ln2", xm_c, lno2_c)
-                    h_c, hid_c = torch.empty(nc, 4 * D, dtype=BF, device=e.dev), torch.empty(nc, 4 * D, dtype=BF, device=e.dev)
-                    xn_c = torch.empty(nc, D, dtype=F32, device=e.dev)
-                    for r0, r1, bw in cgroups:
-                        hip.gemm(lno2_c[r0:r1], bw.wfc, h_c[r0:r1], bias=bw.bfc)
-                        hip.quickgelu(h_c[r0:r1], hid_c[r0:r1])
-                        hip.gemm(hid_c[r0:r1], bw.wpr, xn_c[r0:r1], bias=bw.bpr, resid=xm_c[r0:r1], resid_kind=hip.RESID_F32,
-                                 row_scale=rsc_rows(1, r0, r1))
-                    L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao,
-                             compact=dict(crow=crow, cgroups=cgroups, ao=ao_c, x_mid=xm_c, lno2=lno2_c, h=h_c, hid=hid_c, x_out=xn_c,
-                                          rs=rs_c))
-                    sv["layers"][i] = L
-                    sv["compact"] = xn_c
-                    continue
-                for r0, r1, bw in groups:
-                    hip.gemm(ao[r0:r1], bw.wo, XM[r0:r1], bias=bw.bo, resid=Xc[r0:r1], resid_kind=hip.RESID_F32,
-                             row_scale=rs_rows(rs_a, r0, r1))
-                L["x_mid"] = XM if fresh else XM[r_lo:M].clone()
-                XN = torch.empty(M, D, dtype=F32, device=e.dev) if fresh else Xc
-                lno2 = torch.empty(M, D, dtype=BF, device=e.dev)
-                e._layernorm(segs, "ln2", XM, lno2)
-                h = torch.empty(M, 4 * D, dtype=BF, device=e.dev)
-                hid = torch.empty(M, 4 * D, dtype=BF, device=e.dev)
-                for r0, r1, bw in groups:
-                    if (r1 - r0) % 256 == 0:
-                        # ONE launch writes the pre-activation (the backward's QuickGELU' needs it) and the activation
-                        # (the ping-pong kernel's training forms cover whole 256-row tiles: any other row count takes two launches)
-                        hip.gemm(lno2[r0:r1], bw.wfc, hid[r0:r1], bias=bw.bfc, act=hip.ACT_QUICKGELU, out2=h[r0:r1])
-                    else:
-                        hip.gemm(lno2[r0:r1], bw.wfc, h[r0:r1], bias=bw.bfc)
-                        hip.quickgelu(h[r0:r1], hid[r0:r1])
-                for r0, r1, bw in groups:
-                    hip.gemm(hid[r0:r1], bw.wpr, XN[r0:r1], bias=bw.bpr, resid=XM[r0:r1], resid_kind=hip.RESID_F32,
-                             row_scale=rs_rows(rs_m, r0, r1))
-                L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao, lno2=lno2, h=h, hid=hid)
-                sv["layers"][i] = L
-                Xc = XN
-            if cb is not None and _update_stats:
-                cb.update_running_stats()
-            # ---- heads + loss
-            if sv.get("compact") is not None:
-                # the heads read the compact matrix of the last block's live rows (image cls rows, then EOT rows)
-                sv["x_out"] = sv["compact"]
-                e._head_image(w, Bi, compact=True, x=sv["compact"])
-                e._head_text(w, Bt, compact=True, Bi=Bi, x=sv["compact"])
-            else:
-                sv["x_out"] = Xc if Xc is not X else X[:M].clone()
-                e._head_image(w, Bi, x=Xc)               # the heads read the final residual matrix
-                e._head_text(w, Bt, x=Xc)
-            sv.update(hv=w["hv"].clone(), ht=w["ht"].clone(), fv_raw=w["fv_raw"].clone(), ft_raw=w["ft_raw"].clone(),
-                      fv=w["fv"].clone(), ft=w["ft"].clone(), fvb=w["fvb"].clone(), ftb=w["ftb"].clone(), eot=w["eot"].clone())
-            # ---- loss.  The inference path forms its logits from bf16 unit features (error ~0.03 on a logit at T = 1/0.07:
-            # fine for a loss value, but it perturbs every softmax probability by a few percent and with it the whole
-            # gradient).  The training step splits each fp32 feature into bf16 hi + lo parts and contracts
-            # [hi | hi | lo] . [hi | lo | hi] in one K = 3E GEMM: logits to ~2^-16 relative, still on the bf16 MFMA path.
-            def split(f):
-                hi = hip.cast_bf16(f)
-                lo = hip.cast_bf16(f - hi.float())
-                return torch.cat([hi, lo], dim=1)                                              # [B, 2E]: the gather payload
-            # exp(logit_scale) stays ON THE DEVICE here: as a host scalar (the GEMM's alpha) it would have to be read back after
-            # the previous step's optimizer update, i.e. the host would wait at this point of every forward until the GPU
-            # has finished the step before (measured: forward returned after 83 ms instead of 5 with a step queued) and
-            # then enqueue the backward against a GPU that is already running.  The image features carry the scale instead.
-            s_dev = e.model.logit_scale.detach().float().exp()
-            sv["scale"] = s_dev
-            pi, pt = split(sv["fv"] * s_dev), split(sv["ft"])
-            if not _head:
-                self.saved = sv
-                return pi, pt
-            if C.comm.collectives:
-                allpi, hi_ = C.gather_rows_async(pi)
-                allpt, ht_ = C.gather_rows_async(pt)
-                hi_.wait(); ht_.wait()
-            else:
-                allpi, allpt = pi, pt
-            E = e.E
-            n = allpi.shape[0]
-            off = C.local_label_offset(Bi) if n > Bi else 0
-            sv["off"], sv["n"] = off, n
-            sv["allI"], sv["allT"] = allpi[:, :E].contiguous(), allpt[:, :E].contiguous()     # hi parts: dgrad operands (allI scaled)
-            S_i = _logits(*_logit_operands(pi, allpt, E))                                      # image rows (they carry the scale)
-            S_t = _logits(*_logit_operands(pt, allpi, E))                                      # caption rows
-            lse = torch.empty(2, Bi, dtype=F32, device=e.dev)
-            out = torch.empty(1, dtype=F32, device=e.dev)
-            _loss_partial(S_i, S_t, lse[0], lse[1], off, n, out)
-            sv["coll"] = n > Bi or C.comm.collectives
-            if sv["coll"]:
-                dist.all_reduce(out)
-                lse_flat = torch.empty((n // Bi) * 2, Bi, dtype=F32, device=e.dev)            # concatenated along dim 0: every backend's form
-                dist.all_gather_into_tensor(lse_flat, lse.contiguous())
-                lse_all = lse_flat.view(n // Bi, 2, Bi).permute(1, 0, 2).reshape(2, n).contiguous()   # rank-major global order
-            else:
-                lse_all = lse
-            sv.update(S_i=S_i, S_t=S_t, lse_loc=lse, lse_all=lse_all)
+                if e.vblk[i] is not None and i in e.lateral:
+                    self._adapter_forward(sv, L, i, Xc, cb, conv_events)
+                Xc = self._block_forward(sv, L, i, Xc)
+            pi, pt = self._features(sv, Xc, cb, _update_stats)
+            loss = self._contrastive_loss(sv, pi, pt) if _head else None
             self.saved = sv
-            return out[0].clone()
+            return loss if _head else (pi, pt)
+
+    def _begin_forward(self, img, tok, drop_masks):
+        """The checks, the masks, the held workspace, the captions' staging / packing -> sv, the dict of what backward() reads."""
+        e = self.eng
+        Bi, Bt = img.shape[0], tok.shape[0]
+        assert Bi == Bt, "a training step needs image-text pairs"
+        if drop_masks is not None:
+            drop_masks = self._check_drop_masks(drop_masks, Bi)
+        elif self.drop_path:
+            drop_masks = self.draw_drop_masks(Bi)
+        self.last_drop_masks = drop_masks
+        if e.Lv > hip.ATTENTION_BWD_MAX_L or e.Lt > hip.ATTENTION_BWD_MAX_L:
+            raise NotImplementedError(f"msclip_attention_bwd covers sequences up to {hip.ATTENTION_BWD_MAX_L} tokens")
+        self._release_saved()                                  # a forward that was never differentiated: release its maps
+        w = e._workspace(Bi, Bt)
+        # the conv side's maps (w["stem"], w["par"], w["pool"], S1, P0) -- or the patch-conv model's patch matrix
+        # w["PATCH"] -- are read again by backward(): until then the engine's inference entry points (an eval / logging
+        # call of the same shape in between) get another workspace
+        w["held"] = True
+        # captions run packed like the inference path (engine.text_pack_enabled): rows behind a caption's EOT position
+        # neither influence an output nor receive a gradient.  `tok` may be a batch staged ahead (engine.stage_captions).
+        pack = e.text_pack_enabled()
+        cap = tok if isinstance(tok, Captions) else None
+        tokc = cap.tok if cap is not None else e._check_tok(tok)
+        if pack and cap is None:
+            cap = e.stage_captions(tokc)
+        if not pack:
+            cap = None
+            e._text_unpacked(w, Bt)
+        else:
+            e._text_sizes(cap, w, Bt)                   # the host read (immediate for a batch staged a step ahead)
+        sv = dict(Bi=Bi, Bt=Bt, Mv=w["Mv"], layers=[None] * e.n_layers, tok=tokc, w=w, cap=cap)
+        sv["img"] = e._check_img(img)
+        return sv
+
+    def _conv_side_forward(self, sv):
+        """The fronts (the conv side's maps stay in the workspace `w`; the tokens in front of ln_pre are cloned) and the side
+        stream's share of the conv side -> (the train-mode BatchNorm object or None, the adapters' events or None)."""
+        e, w, Bi = self.eng, sv["w"], sv["Bi"]
+        keep = []
+        cb = None
+        if self.bn == "batch" and not e.patch:             # (the patch-conv model has no BatchNorm: bn is moot there)
+            if self.convbn is None:
+                self.convbn = ConvSideBatchNorm(self)
+            cb = self.convbn
+            cb.begin(sv["img"], w, Bi)
+            cb.front()
+        # unfused=True at every engine call: the conv side runs layer by layer, every map the backward reads stays in `w`
+        e._vision_front(sv["img"], w, Bi, keep_pre=keep, convs_done=cb is not None, unfused=True)
+        sv["tok_pre"] = keep[0]
+        # frozen statistics: the image-only conv branch + the adapters' top-down halves on the engine's side stream, as in
+        # the inference schedule (same-box A/B: 89.6-90.2 -> 88.5-88.9 ms per step)
+        conv_events = None
+        side_ok = not e.patch and gradgemm.lane_enabled() and e.lateral == sorted(e.lateral)
+        if side_ok and cb is None:
+            conv_events = e._conv_branch_on_side_stream(w, Bi, unfused=True)
+        elif side_ok:
+            # train-mode BatchNorm: the same for the raw-conv -> statistics -> normalise chains of the parallel branch and
+            # the adapters' top-down halves (they depend on the image only)
+            if w["Ts"] is None:
+                w["Ts"] = [torch.empty(Bi * e.g * e.g, e.D, dtype=F32, device=e.dev) for _ in e.adapters]
+            side = C.side_stream(e.dev)
+            conv_events = []
+            mine = set(cb.saved)
+            with hip.forked(side) as cur_s:
+                for j in range(len(e.adapters)):
+                    cb.stage(j)
+                    cb.adapter_top(j, w["Ts"][j])
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+                    conv_events.append(ev)
+            # the raw maps and statistics made there come from the side stream's pool; the backward and the running-statistics
+            # update read them on this stream (behind conv_events), which the allocator has to know before they are freed
+            cb.record_stream(cur_s, skip=mine)
+        return cb, conv_events
+
+    def _adapter_forward(self, sv, L, i, Xc, cb, conv_events):
+        """Lateral adapter in front of block i, X[:Mv] <- ln_adapt(token path + top-down map); L["adapter"]: what its backward reads."""
+        e, w, Bi, Mv = self.eng, sv["w"], sv["Bi"], sv["Mv"]
+        j = e.lateral.index(i)
+        a = e.adapters[j]
+        asum = torch.empty(Mv, e.D, dtype=F32, device=e.dev)
+        if cb is not None and conv_events is not None:
+            torch.cuda.current_stream(e.dev).wait_event(conv_events[j])
+            cb.adapter_sum(j, Xc[:Mv], w["Ts"][j], asum)
+        elif cb is not None:
+            cb.stage(j)
+            cb.adapter_top(j, w["T"])
+            cb.adapter_sum(j, Xc[:Mv], w["T"], asum)
+        elif conv_events is not None:
+            torch.cuda.current_stream(e.dev).wait_event(conv_events[j])
+            hip.adapter_sum(Xc[:Mv], w["Ts"][j], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
+        else:
+            e._parallel_stage(j, w, Bi, unfused=True)
+            hip.dwpool(w["par"][j], a["pool"], w["pool"][j], Bi, e.par_hw[j], e.par_hw[j], a["C"], a["k"])
+            hip.gemm(w["pool"][j], a["pw"].weight, w["T"], M=Bi * e.g * e.g, N=a["pw"].cout, bias=a["pw"].bias, ldx=a["pw"].cin)
+            hip.adapter_sum(Xc[:Mv], w["T"], a["dww"], a["dwb"], asum, Bi, e.Lv, e.g, e.usecls)
+        x_pre = Xc[:Mv].clone()                                                   # what the depthwise 3x3 read
+        hip.layernorm(asum, a["ln"].g, a["ln"].b, Xc[:Mv], Mv)                    # X[:Mv] <- ln_adapt(sum), fp32
+        L["adapter"] = dict(j=j, sum=asum, x_pre=x_pre)
+
+    def _block_forward(self, sv, L, i, Xc):
+        """Block i of both towers over the token matrix Xc -> the next block's; sv["layers"][i] = L, what its backward reads."""
+        e, w, Bi, Bt, Mv, M = self.eng, sv["w"], sv["Bi"], sv["Bt"], sv["Mv"], sv["M"]
+        D, dev = e.D, e.dev
+        vb, tb = e.vblk[i], e.tblk[i]
+        segs = ([(0, Mv, vb)] if vb is not None else []) + [(Mv, M, tb)]
+        r_lo = segs[0][0]
+        fresh = r_lo == 0                         # (text block 0 leaves the image rows alone: in place, cloned)
+        L["x_in"] = Xc if fresh else Xc[r_lo:M].clone()
+        # Round 6: behind the LAST block only x[:, 0] of every image (M.py:2685) and the EOT row of every caption (M.py:3057-3060)
+        # are read, and out_proj / ln_2 / c_fc / c_proj are row-wise: they run -- forward here, backward in backward() -- on
+        # those Bi + Bt rows instead of on every token (what the inference path has done since round 3; the rows' gradients
+        # are the only non-zero ones behind the block, so every parameter gradient is unchanged)
+        compact = (i == e.n_layers - 1 and len(segs) == 2 and L["adapter"] is None and options.TRAIN.compact_last_block)
+        XM = None if compact else (torch.empty(M, D, dtype=F32, device=dev) if fresh else Xc)
+        lno1 = torch.empty(M, D, dtype=BF, device=dev)
+        e._layernorm(segs, "ln1", Xc, lno1)        # (both towers' rows in one launch, modality-specific gamma / beta)
+        groups = e._groups(segs)
+        qkv = torch.empty(M, 3 * D, dtype=BF, device=dev)
+        ao = torch.empty(M, D, dtype=BF, device=dev)
+        for r0, r1, bw in groups:
+            hip.gemm(lno1[r0:r1], bw.wqkv, qkv[r0:r1], bias=bw.bqkv)
+        if vb is not None:
+            hip.attention(qkv[:Mv], ao[:Mv], Bi, e.Lv, e.heads, False)
+        e._attention_text(w, qkv, ao, Bt)
+        L.update(r_lo=r_lo, segs=segs, groups=groups, lno1=lno1, qkv=qkv, ao=ao)
+        sv["layers"][i] = L
+        if not compact:
+            L["x_mid"], L["lno2"], L["h"], L["hid"], XN = self._tail_forward(Xc, ao, XM, segs, groups, L["rs"], Mv, True)
+            return XN
+        nc = Bi + Bt
+        crow = torch.cat([torch.arange(0, Mv, e.Lv, dtype=torch.int32, device=dev), w["eot"][:Bt]])   # live rows of X
+        xin_c, ao_c = torch.empty(nc, D, dtype=F32, device=dev), torch.empty(nc, D, dtype=BF, device=dev)
+        hip.gather_rows(Xc, xin_c, nc, row_idx=crow)
+        hip.gather_rows(ao, ao_c, nc, row_idx=crow)
+        csegs = e._live_segs(Bi, Bt, vb, tb)
+        cgroups = e._groups(csegs)
+        xm_c = torch.empty(nc, D, dtype=F32, device=dev)
+        # the compact rows' scales: the table gathered with the same row list as the activations ([2, nc]; a few KB)
+        rs_c = None if L["rs"] is None else torch.stack(L["rs"]).index_select(1, crow.long()).contiguous()
+        xm_c, lno2_c, h_c, hid_c, xn_c = self._tail_forward(xin_c, ao_c, xm_c, csegs, cgroups, rs_c, Bi, False)
+        L["compact"] = dict(crow=crow, cgroups=cgroups, ao=ao_c, x_mid=xm_c, lno2=lno2_c, h=h_c, hid=hid_c, x_out=xn_c, rs=rs_c)
+        sv["compact"] = xn_c
+        return Xc
+
+    def _tail_forward(self, x_in, ao, x_mid, segs, groups, rs, first_row_of_text, fuse_act):
+        """The block's row-wise tail over whatever rows it is given (all tokens, or the last block's live rows): out_proj + residual
+        -> x_mid (the caller's matrix; x_in itself where the block runs in place), ln_2, c_fc, QuickGELU, c_proj + residual
+        -> (x_mid as the backward wants it, lno2, h, hid, x_out).  rs: the two branches' row scales, (attention, MLP) or [2, rows]
+        (None: no stochastic depth).  fuse_act: the all-token call -- c_fc may write activation and pre-activation in one launch,
+        and x_out is allocated in front of ln_2's output as that path always did; the live-row call always takes two launches
+        (the two forms round h differently) and allocates x_out last."""
+        e = self.eng
+        D, dev, r_lo, n = e.D, e.dev, segs[0][0], segs[-1][1]
+        for r0, r1, bw in groups:
+            hip.gemm(ao[r0:r1], bw.wo, x_mid[r0:r1], bias=bw.bo, resid=x_in[r0:r1], resid_kind=hip.RESID_F32,
+                     row_scale=_rs_rows(rs, 0, r0, r1, first_row_of_text))
+        in_place = x_mid is x_in
+        mid = x_mid[r_lo:n].clone() if in_place else x_mid
+        x_out = x_in if in_place else (torch.empty(n, D, dtype=F32, device=dev) if fuse_act else None)
+        lno2 = torch.empty(n, D, dtype=BF, device=dev)
+        e._layernorm(segs, "ln2", x_mid, lno2)
+        h = torch.empty(n, 4 * D, dtype=BF, device=dev)
+        hid = torch.empty(n, 4 * D, dtype=BF, device=dev)
+        if x_out is None:
+            x_out = torch.empty(n, D, dtype=F32, device=dev)
+        for r0, r1, bw in groups:
+            if fuse_act and (r1 - r0) % 256 == 0:
+                # ONE launch writes the pre-activation (the backward's QuickGELU' needs it) and the activation
+                # (the ping-pong kernel's training forms cover whole 256-row tiles: any other row count takes two launches)
+                hip.gemm(lno2[r0:r1], bw.wfc, hid[r0:r1], bias=bw.bfc, act=hip.ACT_QUICKGELU, out2=h[r0:r1])
+            else:
+                hip.gemm(lno2[r0:r1], bw.wfc, h[r0:r1], bias=bw.bfc)
+                hip.quickgelu(h[r0:r1], hid[r0:r1])
+        for r0, r1, bw in groups:
+            hip.gemm(hid[r0:r1], bw.wpr, x_out[r0:r1], bias=bw.bpr, resid=x_mid[r0:r1], resid_kind=hip.RESID_F32,
+                     row_scale=_rs_rows(rs, 1, r0, r1, first_row_of_text))
+        return mid, lno2, h, hid, x_out
+
+    def _features(self, sv, Xc, cb, _update_stats):
+        """Heads, the copies the backward reads -> the gather payloads (pi, pt): bf16 hi | lo of the scaled image / the text features."""
+        e, w, Bi, Bt, M = self.eng, sv["w"], sv["Bi"], sv["Bt"], sv["M"]
+        X = w["X"]
+        if cb is not None and _update_stats:
+            cb.update_running_stats()
+        # ---- heads + loss
+        if sv.get("compact") is not None:
+            # the heads read the compact matrix of the last block's live rows (image cls rows, then EOT rows)
+            sv["x_out"] = sv["compact"]
+            e._head_image(w, Bi, compact=True, x=sv["compact"])
+            e._head_text(w, Bt, compact=True, Bi=Bi, x=sv["compact"])
+        else:
+            sv["x_out"] = Xc if Xc is not X else X[:M].clone()
+            e._head_image(w, Bi, x=Xc)               # the heads read the final residual matrix
+            e._head_text(w, Bt, x=Xc)
+        sv.update(hv=w["hv"].clone(), ht=w["ht"].clone(), fv_raw=w["fv_raw"].clone(), ft_raw=w["ft_raw"].clone(),
+                  fv=w["fv"].clone(), ft=w["ft"].clone(), fvb=w["fvb"].clone(), ftb=w["ftb"].clone(), eot=w["eot"].clone())
+        # exp(logit_scale) stays ON THE DEVICE here: as a host scalar (the GEMM's alpha) it would have to be read back after
+        # the previous step's optimizer update, i.e. the host would wait at this point of every forward until the GPU
+        # has finished the step before (measured: forward returned after 83 ms instead of 5 with a step queued) and
+        # then enqueue the backward against a GPU that is already running.  The image features carry the scale instead.
+        s_dev = e.model.logit_scale.detach().float().exp()
+        sv["scale"] = s_dev
+        return _split_hi_lo(sv["fv"] * s_dev), _split_hi_lo(sv["ft"])
+
+    def _contrastive_loss(self, sv, pi, pt):
+        """Symmetric cross-entropy of this rank's rows against all ranks' -> 0-d loss; what the head's backward reads goes into sv."""
+        e, Bi = self.eng, sv["Bi"]
+        if C.comm.collectives:
+            allpi, hi_ = C.gather_rows_async(pi)
+            allpt, ht_ = C.gather_rows_async(pt)
+            hi_.wait(); ht_.wait()
+        else:
+            allpi, allpt = pi, pt
+        E = e.E
+        n = allpi.shape[0]
+        off = C.local_label_offset(Bi) if n > Bi else 0
+        sv["off"], sv["n"] = off, n
+        sv["allI"], sv["allT"] = allpi[:, :E].contiguous(), allpt[:, :E].contiguous()     # hi parts: dgrad operands (allI scaled)
+        S_i = _logits(*_logit_operands(pi, allpt, E))                                      # image rows (they carry the scale)
+        S_t = _logits(*_logit_operands(pt, allpi, E))                                      # caption rows
+        lse = torch.empty(2, Bi, dtype=F32, device=e.dev)
+        out = torch.empty(1, dtype=F32, device=e.dev)
+        _loss_partial(S_i, S_t, lse[0], lse[1], off, n, out)
+        sv["coll"] = n > Bi or C.comm.collectives
+        if sv["coll"]:
+            dist.all_reduce(out)
+            lse_flat = torch.empty((n // Bi) * 2, Bi, dtype=F32, device=e.dev)            # concatenated along dim 0: every backend's form
+            dist.all_gather_into_tensor(lse_flat, lse.contiguous())
+            lse_all = lse_flat.view(n // Bi, 2, Bi).permute(1, 0, 2).reshape(2, n).contiguous()   # rank-major global order
+        else:
+            lse_all = lse
+        sv.update(S_i=S_i, S_t=S_t, lse_loc=lse, lse_all=lse_all)
+        return out[0].clone()
 
     # ------------------------------------------------------------------ backward
     @hip.off_default_stream
@@ -450,381 +464,40 @@ class TrainStep:
         if sv is None:
             raise RuntimeError("TrainStep.backward() needs the activations of a TrainStep.forward() that has not been "
                                "differentiated yet (call forward first; one backward per forward)")
-        dev, D, E = e.dev, e.D, e.E
-        with torch.cuda.device(dev), torch.no_grad():
-            Bi, Bt, Mv, M = sv["Bi"], sv["Bt"], sv["Mv"], sv["M"]
+        with torch.cuda.device(e.dev), torch.no_grad():
             reducer = C.GradReducer(bucket_bytes) if (reduce and C.comm.collectives) else None
             self.reducer = reducer
-
-            class _Grads(dict):
-                def __setitem__(self, k, v):
-                    dict.__setitem__(self, k, v)
-                    if reducer is not None:
-                        reducer.add(k, v)
-
-                def slot(self, k, shape):
-                    """Where gradient k should be written if it can be born inside its all-reduce bucket (else None)."""
-                    return reducer.reserve(k, shape, dev) if reducer is not None else None
-            grads = _Grads()
-            # Column sums nothing on the critical path reads (LayerNorm parameter gradients, bias gradients): their producers leave
-            # per-block partial matrices, ONE msclip_colsum_multi launch folds all of them behind the transformer's backward (round 5:
-            # ~120 msclip_colsum launches per step, 1.1 ms of the main queue)
-            folds = hip.FoldPlan(dev)
-
-            def fold_into(part, then, scale_n=0, scale=1.0):
-                folds.add(part, then, scale_n=scale_n, scale=scale)
-
-            def ln_param_grads(part, key):
-                """part: (dgamma | dbeta) partials [blocks, 2 C] of a LayerNorm backward -> grads[key.weight], grads[key.bias]."""
-                def then(r):
-                    c = r.shape[0] // 2
-                    grads[key + ".weight"], grads[key + ".bias"] = r[:c], r[c:]
-                fold_into(part, then)
-
-            def set_bias(key, val):
-                """val: the bias gradient itself, or a 2-D matrix of partial sums still to be folded."""
-                if val.dim() == 2:
-                    fold_into(val, lambda r: grads.__setitem__(key, r))
-                else:
-                    grads[key] = val
-            # the four wide weight gradients of a block: operand transposes on the lane at once, the split-K GEMM of job k
-            # on THIS stream when job k + 1 is created (its transposes have run under the kernels issued in between)
-            pending = []
-
-            def flush_wgrads():
-                while pending:
-                    k, job, shape = pending.pop(0)
-                    grads[k] = job.finish(grads.slot(k, shape))
-
-            def wide_wgrad(k, dy, x, rows, shape, post=None):
-                flush_wgrads()
-                pending.append((k, gradgemm.WgradJob(dy, x, rows, post=post), shape))
-            # ---- contrastive head: dL/dS blocks of this rank's image rows and caption rows
-            if _dfeat is not None:
-                dfi, dft, dls = _dfeat
-                grads["logit_scale"] = dls
-            else:
-                dfi, dft, dscale = _clip_head_bwd(e, sv["S_i"], sv["S_t"], sv["allI"], sv["allT"], sv["lse_loc"], sv["lse_all"],
-                                                  sv["off"], sv["n"], sv["scale"])
-                if sv["coll"]:
-                    dist.all_reduce(dscale)
-                # S already carries the scale: dL/dscale = sum G S / scale; logit_scale = log(scale) => dL/dlogit_scale = sum G S
-                grads["logit_scale"] = dscale.reshape(())
-
-            dX = torch.zeros(M, D, dtype=F32, device=dev)
-            if e.patch:
-                conv = None                              # patch-conv stem: its weight gradient at the end (_patch_wgrad)
-            elif self.bn == "batch":
-                conv = self.convbn                       # holds the raw conv outputs / batch statistics of this forward
-            else:
-                conv = ConvSideBackward(self)
-                conv.begin(sv["img"], sv["w"], Bi)
-
-            compact_x = sv.get("compact")                 # [Bi + Bt, D]: the last block ran its row-wise tail on the live rows only
-            dXC = torch.zeros(Bi + Bt, D, dtype=F32, device=dev) if compact_x is not None else None
-
-            def head(feat_raw, dfeat, hrow, w_proj, ln, key_proj, key_ln, row_idx=None, row_mul=1, c0=None):
-                dfr = torch.empty_like(feat_raw)
-                hip.l2norm_bwd(feat_raw, dfeat, dfr)
-                dfr_b = hip.cast_bf16(dfr)
-                grads[key_proj] = _wgrad(hrow, dfr_b, hrow.shape[0])                           # [D, E] like the parameter
-                dh = torch.empty(hrow.shape[0], D, dtype=F32, device=dev)                      # fp32: it feeds column sums
-                hip.gemm(dfr_b, w_proj.t().contiguous(), dh)                                   # dfr [B, E] @ W [E, D]
-                if c0 is not None:                        # compact rows c0 .. of x_out / dXC, one per sample
-                    n_ = hrow.shape[0]
-                    part, _ = hip.layernorm_bwd(sv["x_out"][c0:c0 + n_], dh, ln.g, dXC[c0:c0 + n_], n_, fold=False)
-                else:
-                    part, _ = hip.layernorm_bwd(sv["x_out"], dh, ln.g, dX, hrow.shape[0], row_idx=row_idx, row_mul=row_mul, fold=False)
-                ln_param_grads(part, key_ln)
-            if compact_x is not None:
-                head(sv["fv_raw"], dfi, sv["hv"], e.w_vproj, e.ln_post, "visual.proj", "visual.ln_post", c0=0)
-                head(sv["ft_raw"], dft, sv["ht"], e.w_tproj, e.ln_final, "text_projection", "ln_final", c0=Bi)
-            else:
-                head(sv["fv_raw"], dfi, sv["hv"], e.w_vproj, e.ln_post, "visual.proj", "visual.ln_post", row_mul=e.Lv)
-                head(sv["ft_raw"], dft, sv["ht"], e.w_tproj, e.ln_final, "text_projection", "ln_final", row_idx=sv["eot"])
-
-            def cast_with_bias_sums(dX, dY, r_lo, groups, rs=None):
-                """dY[r_lo:M] = bf16(dX[r_lo:M]) -- the operand of a projection's dgrad / wgrad GEMMs -- and {id(block
-                weights): column sums of the group's rows} = that projection's bias gradient; one pass over dX when a
-                single (shared) weight set covers all rows.  rs (fp32 [M], stochastic depth): copy and sums of rs[row] * dX[row]
-                -- what everything upstream of the projection's scaled residual add sees -- from the same one pass per group."""
-                if rs is not None:
-                    return {id(bw): hip.cast_bf16_colsum(dX[r0:r1], dY[r0:r1], fold=False, row_scale=rs[r0:r1])[1] for r0, r1, bw in groups}
-                if len(groups) == 1 and groups[0][0] == r_lo and groups[0][1] == M:
-                    _, s = hip.cast_bf16_colsum(dX[r_lo:M], dY[r_lo:M], fold=False)    # partial sums: folded with the others (set_bias)
-                    return {id(groups[0][2]): s}
-                hip.cast_bf16(dX[r_lo:M], dY[r_lo:M])
-                return {id(bw): hip.colsum(dX[r0:r1]) for r0, r1, bw in groups}
-
-            # ---- the dgrad GEMMs' W operands: W^T of every projection (bf16 [K, N]; the weights changed in the last optimizer
-            # step), all of them up front on the lane stream with this library's transpose kernel, last block first, one event
-            # per block -- not four ATen transposed copies per block on the main queue (74 launches, 1.8 ms per step)
-            wts, wt_ready = {}, {}
-            if gradgemm.lane_enabled():
-                sets = []
-                for i in reversed(range(e.n_layers)):
-                    for blk in (e.tblk[i], e.vblk[i]):
-                        if blk is not None and all(blk["w"] is not b for b in sets):
-                            sets.append(blk["w"])
-                srcs = [t for bw in sets for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv)]
-                ln_s = gradgemm.lane(dev)
-                with hip.forked(ln_s) as cur_s:
-                    if all(t.shape[0] % 64 == 0 for t in srcs):
-                        # ONE table-driven launch for all of them (48 launches one by one kept the host busy for 0.6 ms at the start
-                        # of the backward, the main queue idle behind it); the table lives while the packed weights do not move
-                        plan = self._wt_plan
-                        if plan is None or plan.key != tuple(t.data_ptr() for t in srcs):
-                            plan = self._wt_plan = hip.TransposePlan(srcs)
-                        outs = plan.run()
-                        done = torch.cuda.Event()
-                        done.record(ln_s)
-                        for j, bw in enumerate(sets):
-                            wts[id(bw)] = tuple(outs[4 * j:4 * j + 4])
-                            wt_ready[id(bw)] = done              # (one launch, one event: whichever weight set is asked for first waits for it)
-                    else:
-                        for bw in sets:
-                            wts[id(bw)] = tuple(hip.transpose_bf16(t, t.shape[0], t.shape[0]) for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv))
-                            for t in wts[id(bw)]:
-                                t.record_stream(cur_s)
-                            wt_ready[id(bw)] = torch.cuda.Event()
-                            wt_ready[id(bw)].record(ln_s)
-
-            def w_t(bw, which):
-                """W^T of block weights bw: 0 c_proj [4D, D]^T.., 1 c_fc, 2 out_proj, 3 in_proj (packed: q rows scaled)."""
-                if id(bw) in wts:
-                    ev = wt_ready.pop(id(bw), None)
-                    if ev is not None:
-                        torch.cuda.current_stream(dev).wait_event(ev)
-                    return wts[id(bw)][which]
-                return (bw.wpr, bw.wfc, bw.wo, bw.wqkv)[which].t().contiguous()
-
-            def ln_bwd_segments(x_saved, dlno, segs, groups, r_lo, which, i, dY_next, rs=None):
-                """LayerNorm backward (`which` = "ln1" / "ln2" of block i) of every row segment: dX += its input gradient.  With
-                dY_next (bf16 [M, D]) the same pass leaves bf16(new dX) there -- the output gradient of the projection in front of
-                this LayerNorm point, operand of its dgrad / wgrad GEMMs -- and returns {id(block weights): that projection's bias
-                gradient} from per-block column sums (no cast_bf16_colsum pass over dX); else returns None.  rs (fp32 [M], with
-                dY_next): that projection sits behind a DropPath -- the copy and the sums of the image rows carry rs[row], dX does not."""
-                parts = {}
-                for r0, r1, b in segs:
-                    kw = {}
-                    if dY_next is not None:
-                        gid = next(id(bw) for g0, g1, bw in groups if g0 <= r0 and r1 <= g1)
-                        first = gid not in parts
-                        if first:
-                            parts[gid] = torch.empty(hip.LN_PART_BLOCKS, D, dtype=F32, device=dev)
-                        kw = dict(dxb=dY_next[r0:r1], sum_part=parts[gid], sum_accumulate=not first,
-                                  row_scale=rs[r0:r1] if (rs is not None and r0 < Mv) else None)
-                    pre = f"visual.transformer.resblocks.{i}" if b is e.vblk[i] else f"transformer.resblocks.{i}"
-                    part, _ = hip.layernorm_bwd(x_saved[r0 - r_lo:r1 - r_lo], dlno[r0:r1], b[which].g, dX[r0:r1], r1 - r0, fold=False, **kw)
-                    ln_param_grads(part, f"{pre}.{'ln_1' if which == 'ln1' else 'ln_2'}")
-                return parts if dY_next is not None else None          # (partial sums: set_bias folds them)
-
+            bp = _BackwardPass(self, sv, reducer)
+            bp.heads(_dfeat)
+            bp.transposed_weights()
             # ---- blocks, last to first
-            fuse_cast = True
             carry = None                      # (dY, bias sums) of this block's MLP half, left by the block above's ln_1 backward
             for i in reversed(range(e.n_layers)):
                 L = sv["layers"][i]
-                r_lo, segs, groups = L["r_lo"], L["segs"], L["groups"]
-                names = {id(e.tblk[i]["w"]): f"transformer.resblocks.{i}"}
-                if e.vblk[i] is not None:                    # shared tensors live under their visual.* name (one Parameter)
-                    names[id(e.vblk[i]["w"])] = f"visual.transformer.resblocks.{i}"
-                cm = L.get("compact")
-                if cm is not None:
-                    # the last block's row-wise tail ran on the Bi + Bt live rows (forward above): its backward on the same rows.  dXC holds
-                    # the heads' gradient wrt the block's output at those rows; every other row's is zero.
+                if L.get("compact") is not None:
                     assert carry is None
-                    nc = Bi + Bt
-                    xm_c, lno2_c, h_c, hid_c, ao_c = cm["x_mid"], cm["lno2"], cm["h"], cm["hid"], cm["ao"]
-                    dlno2_c = torch.empty(nc, D, dtype=F32, device=dev)
-                    rs_c = cm["rs"]                                  # [2, nc] row scales of the live rows (stochastic depth), or None
-
-                    def cast_c(k):
-                        """bf16(dXC) and, per weight group, its column sums -- of rs_c[k][row] * dXC[row] behind a DropPath: one
-                        library pass per group writes the scaled copy and the scaled fp32 rows (a partial row per row), which
-                        the unscaled path's own colsum launch then folds (same shape, same order: scale 1 gives its bits)."""
-                        if rs_c is None:
-                            return hip.cast_bf16(dXC), {id(bw): hip.colsum(dXC[r0:r1]) for r0, r1, bw in cm["cgroups"]}
-                        y = torch.empty(nc, D, dtype=BF, device=dev)
-                        return y, {id(bw): hip.cast_bf16_colsum(dXC[r0:r1], y[r0:r1], row_scale=rs_c[k, r0:r1], blocks=r1 - r0)[1]
-                                   for r0, r1, bw in cm["cgroups"]}
-                    dy_c, bsum_c = cast_c(1)
-                    for r0, r1, bw in cm["cgroups"]:
-                        p = names[id(bw)]
-                        grads[p + ".mlp.c_proj.weight"] = _wgrad(dy_c[r0:r1], hid_c[r0:r1], r1 - r0)
-                        grads[p + ".mlp.c_proj.bias"] = bsum_c[id(bw)]
-                        dh_c = torch.empty(r1 - r0, 4 * D, dtype=BF, device=dev)
-                        hip.quickgelu_bwd(h_c[r0:r1], _dgrad(dy_c[r0:r1], w_t(bw, 0)), dh_c)
-                        grads[p + ".mlp.c_fc.weight"] = _wgrad(dh_c, lno2_c[r0:r1], r1 - r0)
-                        grads[p + ".mlp.c_fc.bias"] = hip.colsum(dh_c)
-                        _dgrad(dh_c, w_t(bw, 1), dlno2_c[r0:r1])
-                    for (c0, c1), b in (((0, Bi), e.vblk[i]), ((Bi, nc), e.tblk[i])):
-                        pre = f"visual.transformer.resblocks.{i}" if b is e.vblk[i] else f"transformer.resblocks.{i}"
-                        part, _ = hip.layernorm_bwd(xm_c[c0:c1], dlno2_c[c0:c1], b["ln2"].g, dXC[c0:c1], c1 - c0, fold=False)
-                        ln_param_grads(part, pre + ".ln_2")
-                    # dXC is now the gradient wrt the rows behind the attention (x_mid): out_proj on the compact rows, then both
-                    # results go back to their rows of the token matrix -- the attention output's gradient (zero elsewhere) and,
-                    # through the residual connection, the block input's
-                    dy2_c, bsum_c = cast_c(0)
-                    dao_c = torch.empty(nc, D, dtype=BF, device=dev)
-                    for r0, r1, bw in cm["cgroups"]:
-                        p = names[id(bw)]
-                        grads[p + ".attn.out_proj.weight"] = _wgrad(dy2_c[r0:r1], ao_c[r0:r1], r1 - r0)
-                        grads[p + ".attn.out_proj.bias"] = bsum_c[id(bw)]
-                        _dgrad(dy2_c[r0:r1], w_t(bw, 2), dao_c[r0:r1])
-                    rows_c = cm["crow"].long()
-                    dao = torch.zeros(M, D, dtype=BF, device=dev)
-                    dao.index_copy_(0, rows_c, dao_c)
-                    dX.index_copy_(0, rows_c, dXC)                   # (dX is still all zero here: nothing but the heads wrote a gradient yet)
-                    dlno = torch.empty(M, D, dtype=F32, device=dev)
-                    dqkv = torch.empty(M, 3 * D, dtype=BF, device=dev)
+                    dlno, dao, dqkv = bp.compact_tail(i, L)
                 else:
-                    hid = L["hid"]
-                    if carry is not None:
-                        dY, bsum = carry
-                        carry = None
-                    else:
-                        dY = torch.empty(M, D, dtype=BF, device=dev)
-                        bsum = cast_with_bias_sums(dX, dY, r_lo, groups, rs=L["rs"][1] if L["rs"] is not None else None)
-                    # gradients of the LayerNorm outputs stay fp32: they are only read by the LayerNorm backward, whose dbeta /
-                    # dgamma are column sums of nearly cancelling terms (a bf16 dy costs 10-30 % on those sums at small batch)
-                    dlno = torch.empty(M, D, dtype=F32, device=dev)
-                    for r0, r1, bw in groups:
-                        p = names[id(bw)]
-                        wide_wgrad(p + ".mlp.c_proj.weight", dY[r0:r1], hid[r0:r1], r1 - r0, (D, 4 * D))
-                        set_bias(p + ".mlp.c_proj.bias", bsum[id(bw)])
-                    dh = torch.empty(M, 4 * D, dtype=BF, device=dev)
-                    dh_part = {}
-                    for r0, r1, bw in groups:
-                        if (r1 - r0) % 256 == 0:
-                            # dh = (dY . W_proj) * QuickGELU'(h): the activation's derivative in the dgrad GEMM's epilogue, which
-                            # also leaves dh's column sums per 128 rows (c_fc's bias gradient without a second pass over dh)
-                            dh_part[id(bw)] = torch.empty((r1 - r0) // 128, 4 * D, dtype=F32, device=dev)
-                            hip.gemm(dY[r0:r1], w_t(bw, 0), dh[r0:r1], resid=L["h"][r0:r1], resid_kind=hip.RESID_GELUGRAD,
-                                     colsum_part=dh_part.get(id(bw)))
-                        else:
-                            dhid = _dgrad(dY[r0:r1], w_t(bw, 0))
-                            hip.quickgelu_bwd(L["h"][r0:r1], dhid, dh[r0:r1])
-                    del hid
-                    for r0, r1, bw in groups:
-                        p = names[id(bw)]
-                        wide_wgrad(p + ".mlp.c_fc.weight", dh[r0:r1], L["lno2"][r0:r1], r1 - r0, (4 * D, D))
-                        if id(bw) in dh_part:
-                            set_bias(p + ".mlp.c_fc.bias", dh_part[id(bw)])
-                        else:
-                            grads[p + ".mlp.c_fc.bias"] = gradgemm.on_lane(lambda a=dh[r0:r1]: hip.colsum(a), dh)
-                        _dgrad(dh[r0:r1], w_t(bw, 1), dlno[r0:r1])
-                    del dh
-                    # attention half.  dX behind the ln_2 backward is out_proj's output gradient: its bf16 copy and bias sums leave with that pass
-                    dY2 = torch.empty(M, D, dtype=BF, device=dev)          # not dY again: the lane stream may still read it (c_proj wgrad)
-                    rs_a = L["rs"][0] if L["rs"] is not None else None
-                    bsum = ln_bwd_segments(L["x_mid"], dlno, segs, groups, r_lo, "ln2", i, dY2 if fuse_cast else None, rs=rs_a)
-                    if bsum is None:
-                        bsum = cast_with_bias_sums(dX, dY2, r_lo, groups, rs=rs_a)
-                    dao = torch.empty(M, D, dtype=BF, device=dev)
-                    dqkv = torch.empty(M, 3 * D, dtype=BF, device=dev)      # attention_bwd writes every row of the towers that ran
-                    for r0, r1, bw in groups:
-                        p = names[id(bw)]
-                        wide_wgrad(p + ".attn.out_proj.weight", dY2[r0:r1], L["ao"][r0:r1], r1 - r0, (D, D))
-                        set_bias(p + ".attn.out_proj.bias", bsum[id(bw)])
-                        _dgrad(dY2[r0:r1], w_t(bw, 2), dao[r0:r1])
-                # the attention backward also leaves every sample's token sums of its dqkv rows (in_proj's bias gradient = their
-                # sum over the samples: 1 024 x 3 D fp32 to fold instead of a second pass over dqkv [M, 3 D]); the query-blocked
-                # form of the long sequences does not carry them
-                qpart = None
-                if e.Lv <= 96 and (sv["cap"] is not None or e.Lt <= 96):
-                    qpart = torch.empty(Bi + Bt, 3 * D, dtype=F32, device=dev)
-                if e.vblk[i] is not None:
-                    hip.attention_bwd(L["qkv"][:Mv], L["ao"][:Mv], dao[:Mv], dqkv[:Mv], Bi, e.Lv, e.heads, False,
-                                      colsum_part=qpart[:Bi] if qpart is not None else None)
-                if sv["cap"] is not None:
-                    hip.attention_bwd_varlen(L["qkv"][Mv:M], L["ao"][Mv:M], dao[Mv:M], dqkv[Mv:M], sv["cap"].cu, Bt, sv["Lmax"],
-                                             e.heads, True, pad_rows=sv["pad"], colsum_part=qpart[Bi:] if qpart is not None else None)
-                else:
-                    hip.attention_bwd(L["qkv"][Mv:M], L["ao"][Mv:M], dao[Mv:M], dqkv[Mv:M], Bt, e.Lt, e.heads, True,
-                                      colsum_part=qpart[Bi:] if qpart is not None else None)
-                for r0, r1, bw in groups:
-                    p = names[id(bw)]
-                    def unscale_q(g):                                                          # packed q rows = 64^-0.5 * W_q
-                        g[:D] *= 0.125
-                        return g
-                    wide_wgrad(p + ".attn.in_proj_weight", dqkv[r0:r1], L["lno1"][r0:r1], r1 - r0, (3 * D, D),
-                               post=unscale_q)                                          # wrt the PACKED weight, scaled back
-                    if qpart is not None:
-                        fold_into(qpart[(0 if r0 < Mv else Bi):(Bi + Bt if r1 > Mv else Bi)],
-                                  lambda r, k=p + ".attn.in_proj_bias": grads.__setitem__(k, r), scale_n=D, scale=0.125)
-                    else:
-                        def bias_q(a=dqkv[r0:r1]):
-                            g = hip.colsum(a)
-                            g[:D] *= 0.125
-                            return g
-                        grads[p + ".attn.in_proj_bias"] = gradgemm.on_lane(bias_q, dqkv)
-                    _dgrad(dqkv[r0:r1], w_t(bw, 3), dlno[r0:r1])
-                # dX behind the ln_1 backward is the output gradient of the block below's c_proj -- unless a lateral adapter's token
-                # path adds to the image rows first, or the block below runs other rows
-                below = sv["layers"][i - 1] if i > 0 else None
-                same = (below is not None and L["adapter"] is None and below["r_lo"] == r_lo and
-                        [(a, b_) for a, b_, _ in below["segs"]] == [(a, b_) for a, b_, _ in segs] and
-                        [(a, b_) for a, b_, _ in below["groups"]] == [(a, b_) for a, b_, _ in groups])
-                dY_below = torch.empty(M, D, dtype=BF, device=dev) if (fuse_cast and same) else None
-                # (behind a DropPath of the block below: its MLP branch's scale rides on this pass)
-                bs = ln_bwd_segments(L["x_in"], dlno, segs, groups, r_lo, "ln1", i, dY_below,
-                                     rs=below["rs"][1] if (dY_below is not None and below["rs"] is not None) else None)
-                if bs is not None:
-                    # keyed by THIS block's weight sets; the block below holds its own: same row ranges, so map by range
-                    by_range = {(g0, g1): bs[id(bw)] for g0, g1, bw in groups}
-                    carry = (dY_below, {id(bw): by_range[(g0, g1)] for g0, g1, bw in below["groups"]})
-                if L["adapter"] is not None:                                                   # token path of the lateral adapter
-                    ad = L["adapter"]
-                    a = e.adapters[ad["j"]]
-                    dsum = torch.empty(Mv, D, dtype=F32, device=dev)
-                    part, _ = hip.layernorm_bwd(ad["sum"], dX[:Mv], a["ln"].g, dsum, Mv, accumulate=False, fold=False)
-                    ln_param_grads(part, f"visual.transformer.parallel_lateral_adapter.{ad['j']}.ln_adapt")
-                    if self.bn == "batch":                               # adapter convs + parallel stage j (train_conv.py)
-                        dgrid, dww = conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
-                    else:
-                        # (moving this chain -- bandwidth-bound, nothing on the critical path reads its products -- to the lane
-                        #  stream was measured: 88.5-88.9 -> 91.0-91.1 ms per step, its kernels take CUs from the dgrad GEMMs)
-                        conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
-                        dgrid, dww = dsum, a["dww"]
-                    hip.adapter_dx(dgrid, dww, dX[:Mv], Bi, e.Lv, e.g, e.usecls)
+                    dlno, carry = bp.mlp(i, L, carry), None
+                    dao, dqkv = bp.out_proj(i, L, dlno)
+                qpart = bp.attention(i, L, dao, dqkv)
+                bp.in_proj(i, L, dqkv, dlno, qpart)
+                carry = bp.ln1_and_carry(i, L, dlno)
+                if L["adapter"] is not None:
+                    bp.adapter(i, L)
                 sv["layers"][i] = None                                                         # free the layer's activations
-            # ---- fronts: text embedding, image cls / positional embeddings, ln_pre
-            # the text rows of dX are final here and nothing below reads the result: the scatter-add (0.67 ms of atomics at
-            # batch 512) runs on the lane, beside the stem's backward
-            dX_text, tok_ids, sv_cap, n_live = dX[Mv:M], sv["tok"], sv["cap"], sv["Mt_live"]
-
-            ne = e.emb.numel()
-
-            def embed_bwd():
-                flat = torch.zeros(ne + e.Lt * D, dtype=F32, device=dev)                     # one tensor: on_lane's contract
-                # the positional embedding's gradient is a sum over the batch: a column sum in a fixed order (bitwise repeatable),
-                # not the kernel's atomics; the token embedding's scatter-add stays atomic (captions share ids)
-                if sv_cap is not None:
-                    # packed rows: scatter-add over the live rows, positional sums over the captions that have the position
-                    hip.embed_tokens_bwd_packed(tok_ids, dX_text[:n_live], sv_cap.cu, flat[:ne].view_as(e.emb), flat[ne:].view(e.Lt, D))
-                elif dX_text.is_contiguous():
-                    hip.embed_tokens_bwd(tok_ids, dX_text, flat[:ne].view_as(e.emb), None)
-                    hip.colsum(dX_text.view(Bt, e.Lt * D), out=flat[ne:])
-                else:
-                    hip.embed_tokens_bwd(tok_ids, dX_text, flat[:ne].view_as(e.emb), flat[ne:].view(e.Lt, D))
-                return flat
-            both = gradgemm.on_lane(embed_bwd, dX_text, tok_ids, *([sv_cap.cu] if sv_cap is not None else []))
-            grads["token_embedding.weight"], grads["positional_embedding"] = both[:ne].view_as(e.emb), both[ne:].view(e.Lt, D)
-            dtok = torch.empty(Mv, D, dtype=F32, device=dev)
-            part, _ = hip.layernorm_bwd(sv["tok_pre"], dX[:Mv], e.ln_pre.g, dtok, Mv, accumulate=False, fold=False)
-            ln_param_grads(part, "visual.ln_pre")
-            dvpos = hip.colsum(dtok.view(Bi, e.Lv * D)).view(e.Lv, D)                           # sum over the batch
-            grads["visual.positional_embedding"] = dvpos
-            grads["visual.class_embedding"] = dvpos[0].clone()
-            folds.run()                                      # every deferred column sum of the transformer's backward, two launches
-            if conv is None:
-                self._patch_wgrad(grads, dtok, sv["w"]["PATCH"], Bi)
+                dlno = dao = dqkv = qpart = None             # (and its gradients: the next block allocates its own)
+            dtok = bp.fronts()
+            bp.folds.run()                                   # every deferred column sum of the transformer's backward, two launches
+            if bp.conv is None:
+                self._patch_wgrad(bp.grads, dtok, sv["w"]["PATCH"], sv["Bi"])
             else:
-                conv.stem(grads, dtok)
-            flush_wgrads()
-            gradgemm.join(dev)                                   # the gradients queued on the lane stream
+                bp.conv.stem(bp.grads, dtok)
+            bp.flush_wgrads()
+            gradgemm.join(e.dev)                                 # the gradients queued on the lane stream
             self._release_saved()
-            return reducer.finish(clone=clone) if reducer is not None else dict(grads)
+            return reducer.finish(clone=clone) if reducer is not None else dict(bp.grads)
+
 
     def _patch_wgrad(self, grads, dtok, patch, Bi):
         """visual.conv1.weight [D, 3, P, P] of the patch-conv stem (M.py:2657; kernel == stride == P, no bias): the forward was
@@ -1285,6 +958,439 @@ def _clip_head_bwd(e, S_i, S_t, allI, allT, lse_loc, lse_all, off, n, scale, bt=
     dfi *= scale                                                                            # d(image features) = scale * G_i @ T_all
     dft, _ = side(S_t, allI, bt[1] if bt else None, lse_loc[1], lse_all[0], False)         # allI already carries the scale
     return dfi, dft, hip.colsum(dsp.view(-1, 1))                                            # sum_r sum_j G S
+
+
+def _rs_rows(rs, k, r0, r1, first_row_of_text):
+    """A launch over rows [r0, r1): its slice of branch k's row scales (text-only launches, or no stochastic depth: none)."""
+    return rs[k][r0:r1] if (rs is not None and r0 < first_row_of_text) else None
+
+
+def _split_hi_lo(f):
+    """---- loss.  The inference path forms its logits from bf16 unit features (error ~0.03 on a logit at T = 1/0.07:
+    fine for a loss value, but it perturbs every softmax probability by a few percent and with it the whole
+    gradient).  The training step splits each fp32 feature into bf16 hi + lo parts and contracts
+    [hi | hi | lo] . [hi | lo | hi] in one K = 3E GEMM: logits to ~2^-16 relative, still on the bf16 MFMA path."""
+    hi = hip.cast_bf16(f)
+    lo = hip.cast_bf16(f - hi.float())
+    return torch.cat([hi, lo], dim=1)                                              # [B, 2E]: the gather payload
+
+
+def _unscale_q(g):                                                                 # packed q rows = 64^-0.5 * W_q
+    g[:g.shape[0] // 3] *= 0.125
+    return g
+
+
+class _Grads(dict):
+    """{key: gradient} of one backward(); with a comm.GradReducer every gradient enters its all-reduce bucket as it is set."""
+
+    def __init__(self, reducer, dev):
+        dict.__init__(self)
+        self.reducer, self.dev = reducer, dev
+
+    def __setitem__(self, k, v):
+        dict.__setitem__(self, k, v)
+        if self.reducer is not None:
+            self.reducer.add(k, v)
+
+    def slot(self, k, shape):
+        """Where gradient k should be written if it can be born inside its all-reduce bucket (else None)."""
+        return self.reducer.reserve(k, shape, self.dev) if self.reducer is not None else None
+
+
+class _BackwardPass:
+    """What the phases of ONE TrainStep.backward() share: the gradients, the deferred column sums, the queue of wide weight
+    gradients, the W^T operands, dX (the gradient of the token matrix, [M, D] fp32) and dXC (of the last block's live rows),
+    the conv side's object.  TrainStep.backward() is the driver that calls the phases in order."""
+
+    def __init__(self, ts, sv, reducer):
+        self.ts, self.e, self.sv = ts, ts.eng, sv
+        self.dev, self.D = self.e.dev, self.e.D
+        self.Bi, self.Bt, self.Mv, self.M = sv["Bi"], sv["Bt"], sv["Mv"], sv["M"]
+        self.grads = _Grads(reducer, self.dev)
+        # Column sums nothing on the critical path reads (LayerNorm parameter gradients, bias gradients): their producers leave
+        # per-block partial matrices, ONE msclip_colsum_multi launch folds all of them behind the transformer's backward (round 5:
+        # ~120 msclip_colsum launches per step, 1.1 ms of the main queue)
+        self.folds = hip.FoldPlan(self.dev)
+        # the four wide weight gradients of a block: operand transposes on the lane at once, the split-K GEMM of job k
+        # on THIS stream when job k + 1 is created (its transposes have run under the kernels issued in between)
+        self.pending = []
+        self.wts, self.wt_ready = {}, {}
+        self.dX = self.dXC = self.conv = None
+
+    def block_key(self, i, b):
+        """state_dict prefix of tower entry b's block i."""
+        return f"visual.transformer.resblocks.{i}" if b is self.e.vblk[i] else f"transformer.resblocks.{i}"
+
+    def names(self, i):
+        """{id(block weights): their prefix} of layer i (one Parameter set under its visual.* name where the towers share it)."""
+        return {id(b["w"]): self.block_key(i, b) for b in (self.e.tblk[i], self.e.vblk[i]) if b is not None}
+
+    def fold_into(self, part, then, scale_n=0, scale=1.0):
+        self.folds.add(part, then, scale_n=scale_n, scale=scale)
+
+    def ln_param_grads(self, part, key):
+        """part: (dgamma | dbeta) partials [blocks, 2 C] of a LayerNorm backward -> grads[key.weight], grads[key.bias]."""
+        grads = self.grads
+
+        def then(r):
+            c = r.shape[0] // 2
+            grads[key + ".weight"], grads[key + ".bias"] = r[:c], r[c:]
+        self.fold_into(part, then)
+
+    def set_bias(self, key, val):
+        """val: the bias gradient itself, or a 2-D matrix of partial sums still to be folded."""
+        grads = self.grads                                   # (the deferred lambda holds the gradients, not this object)
+        if val.dim() == 2:
+            self.fold_into(val, lambda r: grads.__setitem__(key, r))
+        else:
+            grads[key] = val
+
+    def flush_wgrads(self):
+        pending, grads = self.pending, self.grads
+        while pending:
+            k, job, shape = pending.pop(0)
+            grads[k] = job.finish(grads.slot(k, shape))
+
+    def wide_wgrad(self, k, dy, x, rows, shape, post=None):
+        self.flush_wgrads()
+        self.pending.append((k, gradgemm.WgradJob(dy, x, rows, post=post), shape))
+
+    def heads(self, _dfeat):
+        """The contrastive head (or accumulate()'s feature gradients), dX / dXC, the conv side's object, both towers' heads."""
+        ts, e, sv, grads, dev, Bi = self.ts, self.e, self.sv, self.grads, self.dev, self.Bi
+        # ---- contrastive head: dL/dS blocks of this rank's image rows and caption rows
+        if _dfeat is not None:
+            dfi, dft, dls = _dfeat
+            grads["logit_scale"] = dls
+        else:
+            dfi, dft, dscale = _clip_head_bwd(e, sv["S_i"], sv["S_t"], sv["allI"], sv["allT"], sv["lse_loc"], sv["lse_all"],
+                                              sv["off"], sv["n"], sv["scale"])
+            if sv["coll"]:
+                dist.all_reduce(dscale)
+            # S already carries the scale: dL/dscale = sum G S / scale; logit_scale = log(scale) => dL/dlogit_scale = sum G S
+            grads["logit_scale"] = dscale.reshape(())
+        self.dX = torch.zeros(self.M, self.D, dtype=F32, device=dev)
+        if e.patch:
+            self.conv = None                         # patch-conv stem: its weight gradient at the end (_patch_wgrad)
+        elif ts.bn == "batch":
+            self.conv = ts.convbn                    # holds the raw conv outputs / batch statistics of this forward
+        else:
+            self.conv = ConvSideBackward(ts)
+            self.conv.begin(sv["img"], sv["w"], Bi)
+        compact_x = sv.get("compact")                 # [Bi + Bt, D]: the last block ran its row-wise tail on the live rows only
+        self.dXC = torch.zeros(Bi + self.Bt, self.D, dtype=F32, device=dev) if compact_x is not None else None
+        if compact_x is not None:
+            self.head(sv["fv_raw"], dfi, sv["hv"], e.w_vproj, e.ln_post, "visual.proj", "visual.ln_post", c0=0)
+            self.head(sv["ft_raw"], dft, sv["ht"], e.w_tproj, e.ln_final, "text_projection", "ln_final", c0=Bi)
+        else:
+            self.head(sv["fv_raw"], dfi, sv["hv"], e.w_vproj, e.ln_post, "visual.proj", "visual.ln_post", row_mul=e.Lv)
+            self.head(sv["ft_raw"], dft, sv["ht"], e.w_tproj, e.ln_final, "text_projection", "ln_final", row_idx=sv["eot"])
+
+    def head(self, feat_raw, dfeat, hrow, w_proj, ln, key_proj, key_ln, row_idx=None, row_mul=1, c0=None):
+        sv = self.sv
+        dfr = torch.empty_like(feat_raw)
+        hip.l2norm_bwd(feat_raw, dfeat, dfr)
+        dfr_b = hip.cast_bf16(dfr)
+        self.grads[key_proj] = _wgrad(hrow, dfr_b, hrow.shape[0])                      # [D, E] like the parameter
+        dh = torch.empty(hrow.shape[0], self.D, dtype=F32, device=self.dev)            # fp32: it feeds column sums
+        hip.gemm(dfr_b, w_proj.t().contiguous(), dh)                                   # dfr [B, E] @ W [E, D]
+        if c0 is not None:                        # compact rows c0 .. of x_out / dXC, one per sample
+            n_ = hrow.shape[0]
+            part, _ = hip.layernorm_bwd(sv["x_out"][c0:c0 + n_], dh, ln.g, self.dXC[c0:c0 + n_], n_, fold=False)
+        else:
+            part, _ = hip.layernorm_bwd(sv["x_out"], dh, ln.g, self.dX, hrow.shape[0], row_idx=row_idx, row_mul=row_mul, fold=False)
+        self.ln_param_grads(part, key_ln)
+
+    def cast_with_bias_sums(self, dX, dY, r_lo, groups, rs=None):
+        """dY[r_lo:M] = bf16(dX[r_lo:M]) -- the operand of a projection's dgrad / wgrad GEMMs -- and {id(block
+        weights): column sums of the group's rows} = that projection's bias gradient; one pass over dX when a
+        single (shared) weight set covers all rows.  rs (fp32 [M], stochastic depth): copy and sums of rs[row] * dX[row]
+        -- what everything upstream of the projection's scaled residual add sees -- from the same one pass per group."""
+        M = self.M
+        if rs is not None:
+            return {id(bw): hip.cast_bf16_colsum(dX[r0:r1], dY[r0:r1], fold=False, row_scale=rs[r0:r1])[1] for r0, r1, bw in groups}
+        if len(groups) == 1 and groups[0][0] == r_lo and groups[0][1] == M:
+            _, s = hip.cast_bf16_colsum(dX[r_lo:M], dY[r_lo:M], fold=False)    # partial sums: folded with the others (set_bias)
+            return {id(groups[0][2]): s}
+        hip.cast_bf16(dX[r_lo:M], dY[r_lo:M])
+        return {id(bw): hip.colsum(dX[r0:r1]) for r0, r1, bw in groups}
+
+    def transposed_weights(self):
+        """---- the dgrad GEMMs' W operands: W^T of every projection (bf16 [K, N]; the weights changed in the last optimizer
+        step), all of them up front on the lane stream with this library's transpose kernel, last block first, one event
+        per block -- not four ATen transposed copies per block on the main queue (74 launches, 1.8 ms per step)"""
+        ts, e, wts, wt_ready = self.ts, self.e, self.wts, self.wt_ready
+        if not gradgemm.lane_enabled():
+            return
+        sets = []
+        for i in reversed(range(e.n_layers)):
+            for blk in (e.tblk[i], e.vblk[i]):
+                if blk is not None and all(blk["w"] is not b for b in sets):
+                    sets.append(blk["w"])
+        srcs = [t for bw in sets for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv)]
+        ln_s = gradgemm.lane(self.dev)
+        with hip.forked(ln_s) as cur_s:
+            if all(t.shape[0] % 64 == 0 for t in srcs):
+                # ONE table-driven launch for all of them (48 launches one by one kept the host busy for 0.6 ms at the start
+                # of the backward, the main queue idle behind it); the table lives while the packed weights do not move
+                plan = ts._wt_plan
+                if plan is None or plan.key != tuple(t.data_ptr() for t in srcs):
+                    plan = ts._wt_plan = hip.TransposePlan(srcs)
+                outs = plan.run()
+                done = torch.cuda.Event()
+                done.record(ln_s)
+                for j, bw in enumerate(sets):
+                    wts[id(bw)] = tuple(outs[4 * j:4 * j + 4])
+                    wt_ready[id(bw)] = done              # (one launch, one event: whichever weight set is asked for first waits for it)
+            else:
+                for bw in sets:
+                    wts[id(bw)] = tuple(hip.transpose_bf16(t, t.shape[0], t.shape[0]) for t in (bw.wpr, bw.wfc, bw.wo, bw.wqkv))
+                    for t in wts[id(bw)]:
+                        t.record_stream(cur_s)
+                    wt_ready[id(bw)] = torch.cuda.Event()
+                    wt_ready[id(bw)].record(ln_s)
+
+    def w_t(self, bw, which):
+        """W^T of block weights bw: 0 c_proj [4D, D]^T.., 1 c_fc, 2 out_proj, 3 in_proj (packed: q rows scaled)."""
+        if id(bw) in self.wts:
+            ev = self.wt_ready.pop(id(bw), None)
+            if ev is not None:
+                torch.cuda.current_stream(self.dev).wait_event(ev)
+            return self.wts[id(bw)][which]
+        return (bw.wpr, bw.wfc, bw.wo, bw.wqkv)[which].t().contiguous()
+
+    def ln_bwd_segments(self, x_saved, dlno, segs, groups, r_lo, which, i, dY_next, rs=None):
+        """LayerNorm backward (`which` = "ln1" / "ln2" of block i) of every row segment: dX += its input gradient.  With
+        dY_next (bf16 [M, D]) the same pass leaves bf16(new dX) there -- the output gradient of the projection in front of
+        this LayerNorm point, operand of its dgrad / wgrad GEMMs -- and returns {id(block weights): that projection's bias
+        gradient} from per-block column sums (no cast_bf16_colsum pass over dX); else returns None.  rs (fp32 [M], with
+        dY_next): that projection sits behind a DropPath -- the copy and the sums of the image rows carry rs[row], dX does not."""
+        dX, D, dev, Mv = self.dX, self.D, self.dev, self.Mv
+        parts = {}
+        for r0, r1, b in segs:
+            kw = {}
+            if dY_next is not None:
+                gid = next(id(bw) for g0, g1, bw in groups if g0 <= r0 and r1 <= g1)
+                first = gid not in parts
+                if first:
+                    parts[gid] = torch.empty(hip.LN_PART_BLOCKS, D, dtype=F32, device=dev)
+                kw = dict(dxb=dY_next[r0:r1], sum_part=parts[gid], sum_accumulate=not first,
+                          row_scale=rs[r0:r1] if (rs is not None and r0 < Mv) else None)
+            part, _ = hip.layernorm_bwd(x_saved[r0 - r_lo:r1 - r_lo], dlno[r0:r1], b[which].g, dX[r0:r1], r1 - r0, fold=False, **kw)
+            self.ln_param_grads(part, f"{self.block_key(i, b)}.{'ln_1' if which == 'ln1' else 'ln_2'}")
+        return parts if dY_next is not None else None          # (partial sums: set_bias folds them)
+
+    def cast_c(self, cm, k):
+        """bf16(dXC) and, per weight group, its column sums -- of rs_c[k][row] * dXC[row] behind a DropPath: one
+        library pass per group writes the scaled copy and the scaled fp32 rows (a partial row per row), which
+        the unscaled path's own colsum launch then folds (same shape, same order: scale 1 gives its bits)."""
+        dXC, rs_c = self.dXC, cm["rs"]               # rs_c: [2, nc] row scales of the live rows (stochastic depth), or None
+        if rs_c is None:
+            return hip.cast_bf16(dXC), {id(bw): hip.colsum(dXC[r0:r1]) for r0, r1, bw in cm["cgroups"]}
+        y = torch.empty(dXC.shape[0], self.D, dtype=BF, device=self.dev)
+        return y, {id(bw): hip.cast_bf16_colsum(dXC[r0:r1], y[r0:r1], row_scale=rs_c[k, r0:r1], blocks=r1 - r0)[1]
+                   for r0, r1, bw in cm["cgroups"]}
+
+    def compact_tail(self, i, L):
+        """The last block's row-wise tail ran on the Bi + Bt live rows (TrainStep._block_forward): its backward on the same rows.
+        dXC holds the heads' gradient wrt the block's output at those rows; every other row's is zero.
+        -> (dlno, dao, dqkv) for the attention backward and in_proj."""
+        e, grads, dX, dXC, D, dev, Bi, M = self.e, self.grads, self.dX, self.dXC, self.D, self.dev, self.Bi, self.M
+        w_t, names, cm = self.w_t, self.names(i), L["compact"]
+        nc = Bi + self.Bt
+        xm_c, lno2_c, h_c, hid_c, ao_c = cm["x_mid"], cm["lno2"], cm["h"], cm["hid"], cm["ao"]
+        dlno2_c = torch.empty(nc, D, dtype=F32, device=dev)
+        dy_c, bsum_c = self.cast_c(cm, 1)
+        for r0, r1, bw in cm["cgroups"]:
+            p = names[id(bw)]
+            grads[p + ".mlp.c_proj.weight"] = _wgrad(dy_c[r0:r1], hid_c[r0:r1], r1 - r0)
+            grads[p + ".mlp.c_proj.bias"] = bsum_c[id(bw)]
+            dh_c = torch.empty(r1 - r0, 4 * D, dtype=BF, device=dev)
+            hip.quickgelu_bwd(h_c[r0:r1], _dgrad(dy_c[r0:r1], w_t(bw, 0)), dh_c)
+            grads[p + ".mlp.c_fc.weight"] = _wgrad(dh_c, lno2_c[r0:r1], r1 - r0)
+            grads[p + ".mlp.c_fc.bias"] = hip.colsum(dh_c)
+            _dgrad(dh_c, w_t(bw, 1), dlno2_c[r0:r1])
+        for (c0, c1), b in (((0, Bi), e.vblk[i]), ((Bi, nc), e.tblk[i])):
+            part, _ = hip.layernorm_bwd(xm_c[c0:c1], dlno2_c[c0:c1], b["ln2"].g, dXC[c0:c1], c1 - c0, fold=False)
+            self.ln_param_grads(part, self.block_key(i, b) + ".ln_2")
+        # dXC is now the gradient wrt the rows behind the attention (x_mid): out_proj on the compact rows, then both
+        # results go back to their rows of the token matrix -- the attention output's gradient (zero elsewhere) and,
+        # through the residual connection, the block input's
+        dy2_c, bsum_c = self.cast_c(cm, 0)
+        dao_c = torch.empty(nc, D, dtype=BF, device=dev)
+        for r0, r1, bw in cm["cgroups"]:
+            p = names[id(bw)]
+            grads[p + ".attn.out_proj.weight"] = _wgrad(dy2_c[r0:r1], ao_c[r0:r1], r1 - r0)
+            grads[p + ".attn.out_proj.bias"] = bsum_c[id(bw)]
+            _dgrad(dy2_c[r0:r1], w_t(bw, 2), dao_c[r0:r1])
+        rows_c = cm["crow"].long()
+        dao = torch.zeros(M, D, dtype=BF, device=dev)
+        dao.index_copy_(0, rows_c, dao_c)
+        dX.index_copy_(0, rows_c, dXC)                   # (dX is still all zero here: nothing but the heads wrote a gradient yet)
+        dlno = torch.empty(M, D, dtype=F32, device=dev)
+        dqkv = torch.empty(M, 3 * D, dtype=BF, device=dev)
+        return dlno, dao, dqkv
+
+    def mlp(self, i, L, carry):
+        """MLP half of block i over all rows -> dlno, ln_2's output gradient.  carry: (dY, bias sums) or None (cast here)."""
+        dX, D, dev, M, w_t, names = self.dX, self.D, self.dev, self.M, self.w_t, self.names(i)
+        r_lo, groups = L["r_lo"], L["groups"]
+        hid = L["hid"]
+        if carry is not None:
+            dY, bsum = carry
+        else:
+            dY = torch.empty(M, D, dtype=BF, device=dev)
+            bsum = self.cast_with_bias_sums(dX, dY, r_lo, groups, rs=L["rs"][1] if L["rs"] is not None else None)
+        # gradients of the LayerNorm outputs stay fp32: they are only read by the LayerNorm backward, whose dbeta /
+        # dgamma are column sums of nearly cancelling terms (a bf16 dy costs 10-30 % on those sums at small batch)
+        dlno = torch.empty(M, D, dtype=F32, device=dev)
+        for r0, r1, bw in groups:
+            p = names[id(bw)]
+            self.wide_wgrad(p + ".mlp.c_proj.weight", dY[r0:r1], hid[r0:r1], r1 - r0, (D, 4 * D))
+            self.set_bias(p + ".mlp.c_proj.bias", bsum[id(bw)])
+        dh = torch.empty(M, 4 * D, dtype=BF, device=dev)
+        dh_part = {}
+        for r0, r1, bw in groups:
+            if (r1 - r0) % 256 == 0:
+                # dh = (dY . W_proj) * QuickGELU'(h): the activation's derivative in the dgrad GEMM's epilogue, which
+                # also leaves dh's column sums per 128 rows (c_fc's bias gradient without a second pass over dh)
+                dh_part[id(bw)] = torch.empty((r1 - r0) // 128, 4 * D, dtype=F32, device=dev)
+                hip.gemm(dY[r0:r1], w_t(bw, 0), dh[r0:r1], resid=L["h"][r0:r1], resid_kind=hip.RESID_GELUGRAD,
+                         colsum_part=dh_part.get(id(bw)))
+            else:
+                dhid = _dgrad(dY[r0:r1], w_t(bw, 0))
+                hip.quickgelu_bwd(L["h"][r0:r1], dhid, dh[r0:r1])
+        del hid
+        for r0, r1, bw in groups:
+            p = names[id(bw)]
+            self.wide_wgrad(p + ".mlp.c_fc.weight", dh[r0:r1], L["lno2"][r0:r1], r1 - r0, (4 * D, D))
+            if id(bw) in dh_part:
+                self.set_bias(p + ".mlp.c_fc.bias", dh_part[id(bw)])
+            else:
+                self.grads[p + ".mlp.c_fc.bias"] = gradgemm.on_lane(lambda a=dh[r0:r1]: hip.colsum(a), dh)
+            _dgrad(dh[r0:r1], w_t(bw, 1), dlno[r0:r1])
+        del dh
+        return dlno
+
+    def out_proj(self, i, L, dlno):
+        """attention half.  dX behind the ln_2 backward is out_proj's output gradient: its bf16 copy and bias sums leave with that pass
+        -> (dao, dqkv): the attention output's gradient and the matrix the attention backward writes."""
+        D, dev, M, names = self.D, self.dev, self.M, self.names(i)
+        r_lo, segs, groups = L["r_lo"], L["segs"], L["groups"]
+        dY2 = torch.empty(M, D, dtype=BF, device=dev)          # not dY again: the lane stream may still read it (c_proj wgrad)
+        rs_a = L["rs"][0] if L["rs"] is not None else None
+        bsum = self.ln_bwd_segments(L["x_mid"], dlno, segs, groups, r_lo, "ln2", i, dY2, rs=rs_a)
+        dao = torch.empty(M, D, dtype=BF, device=dev)
+        dqkv = torch.empty(M, 3 * D, dtype=BF, device=dev)      # attention_bwd writes every row of the towers that ran
+        for r0, r1, bw in groups:
+            p = names[id(bw)]
+            self.wide_wgrad(p + ".attn.out_proj.weight", dY2[r0:r1], L["ao"][r0:r1], r1 - r0, (D, D))
+            self.set_bias(p + ".attn.out_proj.bias", bsum[id(bw)])
+            _dgrad(dY2[r0:r1], self.w_t(bw, 2), dao[r0:r1])
+        return dao, dqkv
+
+    def attention(self, i, L, dao, dqkv):
+        """the attention backward also leaves every sample's token sums of its dqkv rows (in_proj's bias gradient = their
+        sum over the samples: 1 024 x 3 D fp32 to fold instead of a second pass over dqkv [M, 3 D]); the query-blocked
+        form of the long sequences does not carry them -> those sums (qpart, [Bi + Bt, 3 D]) or None."""
+        e, sv, Bi, Bt, Mv, M = self.e, self.sv, self.Bi, self.Bt, self.Mv, self.M
+        qpart = None
+        if e.Lv <= 96 and (sv["cap"] is not None or e.Lt <= 96):
+            qpart = torch.empty(Bi + Bt, 3 * self.D, dtype=F32, device=self.dev)
+        if e.vblk[i] is not None:
+            hip.attention_bwd(L["qkv"][:Mv], L["ao"][:Mv], dao[:Mv], dqkv[:Mv], Bi, e.Lv, e.heads, False,
+                              colsum_part=qpart[:Bi] if qpart is not None else None)
+        if sv["cap"] is not None:
+            hip.attention_bwd_varlen(L["qkv"][Mv:M], L["ao"][Mv:M], dao[Mv:M], dqkv[Mv:M], sv["cap"].cu, Bt, sv["Lmax"],
+                                     e.heads, True, pad_rows=sv["pad"], colsum_part=qpart[Bi:] if qpart is not None else None)
+        else:
+            hip.attention_bwd(L["qkv"][Mv:M], L["ao"][Mv:M], dao[Mv:M], dqkv[Mv:M], Bt, e.Lt, e.heads, True,
+                              colsum_part=qpart[Bi:] if qpart is not None else None)
+        return qpart
+
+    def in_proj(self, i, L, dqkv, dlno, qpart):
+        """in_proj of block i: weight gradient, bias gradient (from qpart, or dqkv's column sums on the lane), dlno <- ln_1's."""
+        grads, D, Bi, Bt, Mv, names = self.grads, self.D, self.Bi, self.Bt, self.Mv, self.names(i)
+        for r0, r1, bw in L["groups"]:
+            p = names[id(bw)]
+            self.wide_wgrad(p + ".attn.in_proj_weight", dqkv[r0:r1], L["lno1"][r0:r1], r1 - r0, (3 * D, D),
+                            post=_unscale_q)                                        # wrt the PACKED weight, scaled back
+            if qpart is not None:
+                self.fold_into(qpart[(0 if r0 < Mv else Bi):(Bi + Bt if r1 > Mv else Bi)],
+                               lambda r, k=p + ".attn.in_proj_bias": grads.__setitem__(k, r), scale_n=D, scale=0.125)
+            else:
+                grads[p + ".attn.in_proj_bias"] = gradgemm.on_lane(lambda a=dqkv[r0:r1]: _unscale_q(hip.colsum(a)), dqkv)
+            _dgrad(dqkv[r0:r1], self.w_t(bw, 3), dlno[r0:r1])
+
+    def ln1_and_carry(self, i, L, dlno):
+        """dX behind the ln_1 backward is the output gradient of the block below's c_proj -- unless a lateral adapter's token
+        path adds to the image rows first, or the block below runs other rows -> the block below's carry, (dY, bias sums), or None."""
+        r_lo, segs, groups = L["r_lo"], L["segs"], L["groups"]
+        below = self.sv["layers"][i - 1] if i > 0 else None
+        same = (below is not None and L["adapter"] is None and below["r_lo"] == r_lo and
+                [(a, b_) for a, b_, _ in below["segs"]] == [(a, b_) for a, b_, _ in segs] and
+                [(a, b_) for a, b_, _ in below["groups"]] == [(a, b_) for a, b_, _ in groups])
+        dY_below = torch.empty(self.M, self.D, dtype=BF, device=self.dev) if same else None
+        # (behind a DropPath of the block below: its MLP branch's scale rides on this pass)
+        bs = self.ln_bwd_segments(L["x_in"], dlno, segs, groups, r_lo, "ln1", i, dY_below,
+                                  rs=below["rs"][1] if (dY_below is not None and below["rs"] is not None) else None)
+        if bs is None:
+            return None
+        # keyed by THIS block's weight sets; the block below holds its own: same row ranges, so map by range
+        by_range = {(g0, g1): bs[id(bw)] for g0, g1, bw in groups}
+        return (dY_below, {id(bw): by_range[(g0, g1)] for g0, g1, bw in below["groups"]})
+
+    def adapter(self, i, L):
+        """token path of the lateral adapter in front of block i (its convolutions: train_conv.py)."""
+        e, dX, Mv, conv, grads = self.e, self.dX, self.Mv, self.conv, self.grads
+        ad = L["adapter"]
+        a = e.adapters[ad["j"]]
+        dsum = torch.empty(Mv, self.D, dtype=F32, device=self.dev)
+        part, _ = hip.layernorm_bwd(ad["sum"], dX[:Mv], a["ln"].g, dsum, Mv, accumulate=False, fold=False)
+        self.ln_param_grads(part, f"visual.transformer.parallel_lateral_adapter.{ad['j']}.ln_adapt")
+        if self.ts.bn == "batch":                            # adapter convs + parallel stage j (train_conv.py)
+            dgrid, dww = conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
+        else:
+            # (moving this chain -- bandwidth-bound, nothing on the critical path reads its products -- to the lane
+            #  stream was measured: 88.5-88.9 -> 91.0-91.1 ms per step, its kernels take CUs from the dgrad GEMMs)
+            conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
+            dgrid, dww = dsum, a["dww"]
+        hip.adapter_dx(dgrid, dww, dX[:Mv], self.Bi, e.Lv, e.g, e.usecls)
+
+    def embed_bwd(self):
+        """Token and text positional embedding gradients as ONE flat tensor (on_lane's contract), from the text rows of dX."""
+        e, sv, D, Mv = self.e, self.sv, self.D, self.Mv
+        dX_text, tok_ids, sv_cap, n_live, ne = self.dX[Mv:self.M], sv["tok"], sv["cap"], sv["Mt_live"], e.emb.numel()
+        flat = torch.zeros(ne + e.Lt * D, dtype=F32, device=self.dev)                     # one tensor: on_lane's contract
+        # the positional embedding's gradient is a sum over the batch: a column sum in a fixed order (bitwise repeatable),
+        # not the kernel's atomics; the token embedding's scatter-add stays atomic (captions share ids)
+        if sv_cap is not None:
+            # packed rows: scatter-add over the live rows, positional sums over the captions that have the position
+            hip.embed_tokens_bwd_packed(tok_ids, dX_text[:n_live], sv_cap.cu, flat[:ne].view_as(e.emb), flat[ne:].view(e.Lt, D))
+        elif dX_text.is_contiguous():
+            hip.embed_tokens_bwd(tok_ids, dX_text, flat[:ne].view_as(e.emb), None)
+            hip.colsum(dX_text.view(self.Bt, e.Lt * D), out=flat[ne:])
+        else:
+            hip.embed_tokens_bwd(tok_ids, dX_text, flat[:ne].view_as(e.emb), flat[ne:].view(e.Lt, D))
+        return flat
+
+    def fronts(self):
+        """---- fronts: text embedding, image cls / positional embeddings, ln_pre -> dtok, the gradient of the image tokens in
+        front of ln_pre (the stem's, or the patch weight's, input gradient)."""
+        e, sv, grads, dX, D, Mv = self.e, self.sv, self.grads, self.dX, self.D, self.Mv
+        # the text rows of dX are final here and nothing below reads the result: the scatter-add (0.67 ms of atomics at
+        # batch 512) runs on the lane, beside the stem's backward
+        ne = e.emb.numel()
+        both = gradgemm.on_lane(self.embed_bwd, dX[Mv:self.M], sv["tok"], *([sv["cap"].cu] if sv["cap"] is not None else []))
+        grads["token_embedding.weight"], grads["positional_embedding"] = both[:ne].view_as(e.emb), both[ne:].view(e.Lt, D)
+        dtok = torch.empty(Mv, D, dtype=F32, device=self.dev)
+        part, _ = hip.layernorm_bwd(sv["tok_pre"], dX[:Mv], e.ln_pre.g, dtok, Mv, accumulate=False, fold=False)
+        self.ln_param_grads(part, "visual.ln_pre")
+        dvpos = hip.colsum(dtok.view(self.Bi, e.Lv * D)).view(e.Lv, D)                      # sum over the batch
+        grads["visual.positional_embedding"] = dvpos
+        grads["visual.class_embedding"] = dvpos[0].clone()
+        return dtok
+
 
 
 class _Accumulators:
