@@ -154,7 +154,10 @@ const char* msclip_gemm_variant(const msclip_gemm_desc* desc);
 
 /* Fused softmax(q k^T [+ causal]) v per (sample, head), head_dim 64, L <= 288 (257 = the 16 x 16 grid of a 14-pixel patch); q pre-scaled.
  * qkv: bf16 [nsamples*L, ldq] with columns [q | k | v], each heads*64 wide.  out: bf16
- * [nsamples*L, ldo], ldq % 8 == 0 and ldo % 8 == 0 (16-byte row pieces).  Replaces M.py:707-738 (scale, reshapes, bmm, mask add, softmax, bmm). */
+ * [nsamples*L, ldo], ldq % 8 == 0 and ldo % 8 == 0 (16-byte row pieces).  Replaces M.py:707-738 (scale, reshapes, bmm, mask add, softmax, bmm).
+ * Leading dimensions, here and in every attention entry point below: any multiple of 8 with ldq >= 3*heads*64 and ldo >= heads*64
+ * (ldqc >= heads*64 for the compact query rows); a narrower one is MSCLIP_EINVAL.  Only the live rows' own columns are read and
+ * written (tests/attention_forms.py states the contract per element). */
 int msclip_attention(const void* qkv, void* out, int nsamples, int L, int heads, int ldq, int ldo, int causal,
                      void* stream);
 
@@ -453,7 +456,8 @@ int msclip_layernorm_bwd(const float* x, int ldx, const int* row_idx, int row_mu
  * of a caption (M.py:3057-3060) is read afterwards.  q: bf16 [nsamples, ldqc] = the (pre-scaled) query rows; qkv: the token
  * matrix of msclip_attention -- only its k | v columns are read (the q columns may hold anything); sample b's keys are rows
  * row_base + b*L ... and their count is last_row ? last_row[b] - (row_base + b*L) + 1 : L (a causal query at its own position
- * sees the keys up to itself; NULL = all L keys).  out: bf16 [nsamples, ldo].  L <= 256; ldqc, ldq, ldo multiples of 8. */
+ * sees the keys up to itself; NULL = all L keys).  out: bf16 [nsamples, ldo].  L <= 288; ldqc, ldq, ldo multiples of 8,
+ * ldqc >= heads*64, ldq >= 3*heads*64, ldo >= heads*64. */
 int msclip_attention_lastq(const void* q, int ldqc, const void* qkv, int ldq, void* out, int ldo, int nsamples, int L, int heads,
                            const int* last_row, int row_base, void* stream);
 

@@ -643,6 +643,7 @@ extern "C" int msclip_attention(const void* qkv, void* out, int nsamples, int L,
                                 int causal, void* stream) {
   MSCLIP_PLAN_HOOK(msclip_attention, stream, qkv, out, nsamples, L, heads, ldq, ldo, causal);
   if (!qkv || !out || nsamples <= 0 || L <= 0 || heads <= 0 || (ldq % 8) || (ldo % 8)) return MSCLIP_EINVAL;
+  if (ldq < 3 * heads * 64 || ldo < heads * 64) return MSCLIP_EINVAL;       // a row holds q | k | v (the heads' outputs) side by side
   hipStream_t st = (hipStream_t)stream;
   if (L <= 64) return launch<2>(qkv, out, nsamples, L, heads, ldq, ldo, causal, st);
   if (L <= 96) return launch<3>(qkv, out, nsamples, L, heads, ldq, ldo, causal, st);
@@ -659,6 +660,7 @@ static int lastq_launch(const void* q, int ldqc, const void* qkv, int ldq, void*
                         const int* last_row, int row_base, const int* cu, void* stream) {
   if (!q || !qkv || !out || nsamples <= 0 || L <= 0 || L > 288 || heads <= 0 || (ldqc % 8) || (ldq % 8) || (ldo % 8) || ldo < heads * 64 || row_base < 0)
     return MSCLIP_EINVAL;
+  if (ldq < 3 * heads * 64 || ldqc < heads * 64) return MSCLIP_EINVAL;
   const int grid = (nsamples * heads + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
 #define LASTQ(MAXI)                                                                                                            \
@@ -693,6 +695,7 @@ extern "C" int msclip_attention_varlen(const void* qkv, void* out, const int* cu
   if (!qkv || !out || !cu || nsamples <= 0 || Lmax <= 0 || Lmax > 96 || heads <= 0 || (ldq % 8) || (ldo % 8) || pad_rows < 0 ||
       pad_rows > 255)
     return MSCLIP_EINVAL;
+  if (ldq < 3 * heads * 64 || ldo < heads * 64) return MSCLIP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (Lmax <= 32) return launch<1>(qkv, out, nsamples, Lmax, heads, ldq, ldo, causal, st, cu, pad_rows, dims);
   if (Lmax <= 64) return launch<2>(qkv, out, nsamples, Lmax, heads, ldq, ldo, causal, st, cu, pad_rows, dims);

@@ -628,6 +628,7 @@ extern "C" int msclip_attention_bwd(const void* qkv, const void* o, const void* 
   MSCLIP_PLAN_HOOK(msclip_attention_bwd, stream, qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, causal, colsum_part);
   if (!qkv || !o || !dout || !dqkv || nsamples <= 0 || L <= 0 || L > 272 || heads <= 0 || (ldq % 8) || (ldo % 8))
     return MSCLIP_EINVAL;
+  if (ldq < 3 * heads * 64 || ldo < heads * 64) return MSCLIP_EINVAL;       // a row holds q | k | v (the heads' outputs) side by side
   if (colsum_part && L > 96) return MSCLIP_EINVAL;      // the query-blocked form does not carry the per-sample column sums
   hipStream_t st = (hipStream_t)stream;
   if (L > 208) return causal ? launch_bwd_qb<17, true, true>(qkv, o, dout, dqkv, nsamples, L, heads, ldq, ldo, st)
@@ -649,6 +650,7 @@ extern "C" int msclip_attention_bwd_varlen(const void* qkv, const void* o, const
   if (!qkv || !o || !dout || !dqkv || !cu || nsamples <= 0 || Lmax <= 0 || Lmax > 96 || heads <= 0 || (ldq % 8) || (ldo % 8) ||
       pad_rows < 0 || pad_rows > 255)
     return MSCLIP_EINVAL;
+  if (ldq < 3 * heads * 64 || ldo < heads * 64) return MSCLIP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (Lmax <= 32) return causal ? launch_bwd<2, true>(qkv, o, dout, dqkv, nsamples, Lmax, heads, ldq, ldo, st, cu, pad_rows, colsum_part)
                                 : launch_bwd<2, false>(qkv, o, dout, dqkv, nsamples, Lmax, heads, ldq, ldo, st, cu, pad_rows, colsum_part);
