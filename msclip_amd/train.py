@@ -1348,13 +1348,10 @@ class _BackwardPass:
         dsum = torch.empty(Mv, self.D, dtype=F32, device=self.dev)
         part, _ = hip.layernorm_bwd(ad["sum"], dX[:Mv], a["ln"].g, dsum, Mv, accumulate=False, fold=False)
         self.ln_param_grads(part, f"visual.transformer.parallel_lateral_adapter.{ad['j']}.ln_adapt")
-        if self.ts.bn == "batch":                            # adapter convs + parallel stage j (train_conv.py)
-            dgrid, dww = conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
-        else:
-            # (moving this chain -- bandwidth-bound, nothing on the critical path reads its products -- to the lane
-            #  stream was measured: 88.5-88.9 -> 91.0-91.1 ms per step, its kernels take CUs from the dgrad GEMMs)
-            conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
-            dgrid, dww = dsum, a["dww"]
+        # adapter convs + parallel stage j (train_conv.py) -> the gradient matrix and depthwise filter of the token path
+        # (moving the frozen walk's chain -- bandwidth-bound, nothing on the critical path reads its products -- to the lane
+        #  stream was measured: 88.5-88.9 -> 91.0-91.1 ms per step, its kernels take CUs from the dgrad GEMMs)
+        dgrid, dww = conv.adapter(grads, ad["j"], dsum, ad["x_pre"])
         hip.adapter_dx(dgrid, dww, dX[:Mv], self.Bi, e.Lv, e.g, e.usecls)
 
     def embed_bwd(self):

@@ -2,12 +2,13 @@
 stem (M.py:1898-2000), the parallel convolutional branch (M.py:1812-1895) and the convolutional halves of the lateral
 adapters (M.py:1752-1778).
 
-Two BatchNorm semantics.  ConvSideBackward (first half of this file): FROZEN statistics -- the HIP forward folds every
-BatchNorm's running mean / variance into the adjacent convolution (packing.py) and the backward differentiates exactly
-that function: gamma, beta and the convolution weights receive gradients, the running statistics are constants (what
-autograd of the reference gives in eval() mode; fixture tests/golden/*.grads.npz).  ConvSideBatchNorm (second half):
-train-mode BatchNorm with per-GPU batch statistics, their backward and the running-statistics update (the reference in
-train() mode; fixture tests/golden/b32-yfcc-msclips.grads_trainbn.npz).
+Three parts.  ConvGrad: the gradients of ONE convolution (weight and input gradient, ReLU backward, the image's patch matrix)
+and the W^T operand cache; no BatchNorm in it.  Two walks, each with a ConvGrad and hand-over state of its own, one per BatchNorm
+semantics.  ConvSideBackward: FROZEN statistics -- the HIP forward folds every BatchNorm's running mean / variance into the
+adjacent convolution (packing.py) and the backward differentiates exactly that function: gamma, beta and the convolution weights
+receive gradients, the running statistics are constants (what autograd of the reference gives in eval() mode; fixture
+tests/golden/*.grads.npz).  ConvSideBatchNorm: train-mode BatchNorm with per-GPU batch statistics, their backward and the
+running-statistics update (the reference in train() mode; fixture tests/golden/b32-yfcc-msclips.grads_trainbn.npz).
 
 Every convolution is a GEMM in the forward (implicit im2col gather); here
     dWf = dY^T . im2col(X)      msclip_im2col + the split-K wgrad GEMM (gradgemm.wgrad)
@@ -20,11 +21,14 @@ its 3x3 (packing.stem_stage): its gradient is the centre tap of the merged filte
 Activations are read from the engine's workspace (the training forward asks the engine for the conv side layer by layer,
 unfused=True, so every intermediate map is there): valid until the next forward on the same batch shape.
 """
+from collections import namedtuple
+
 import torch
 
 from . import gradgemm
 from . import hip
 from . import options
+from . import packing as P
 from .gradgemm import wgrad as _wgrad, wgrad_async as _wgrad_async
 
 BF = torch.bfloat16
@@ -58,35 +62,43 @@ class _Fold:
         (one launch: msclip_bn_fold_bwd)."""
         Gc = G if G.is_contiguous() else G.contiguous()
         dW, dg, db = hip.bn_fold_bwd(Gc, w_raw.contiguous(), dshift.contiguous(), self.gamma, self.mean, self.var, self.eps)
-        out[conv_key] = dW
-        out[self.prefix + ".weight"] = dg
-        out[self.prefix + ".bias"] = db
+        out[conv_key], out[self.prefix + ".weight"], out[self.prefix + ".bias"] = dW, dg, db
 
 
 _PARITY_PLANS = {}
 
 
-def _image_kalign():
-    return 32
+def _pointwise(spec):
+    return (spec.kh, spec.kw, spec.stride, spec.pad) == (1, 1, 1, 0)
 
 
-class ConvSideBackward:
-    def __init__(self, train_step):
-        self.ts = train_step
-        self.e = train_step.eng
-        self._wt = {}
+class ConvGrad:
+    """The gradients of single convolutions, for both walks below.  Owns the W^T operands of the input-gradient GEMMs (valid for
+    one set of weight values: begin() drops them), the process-wide parity plans, the image and batch of the current step and
+    the patch matrix of that image, built when first asked for."""
+
+    def __init__(self, engine):
+        self.e = engine
         self._pplan = _PARITY_PLANS                      # parity-class dgrad plans (geometry only: survive weight updates)
+        self.begin(None, None)
 
-    # ------------------------------------------------------------------ generic pieces
+    def begin(self, img, Bi):
+        """Once per step: transposed weights of the previous step are stale, and so is its image's patch matrix."""
+        self.img, self.Bi, self.col_img, self._wt = img, Bi, None, {}
+
+    def transposed(self, key, make):
+        """The W^T operand `key` of this step: make() on first use."""
+        if key not in self._wt:
+            self._wt[key] = make()
+        return self._wt[key]
+
     def _w_t(self, key, weight, cout, cin_cols):
         """Folded forward weight [cout, Kp] bf16 -> [Kp or cin_cols, cout padded to 64] bf16: the dgrad GEMM's W operand."""
-        t = self._wt.get(key)
-        if t is None:
-            cp = (cout + 63) // 64 * 64
-            t = torch.zeros(cin_cols, cp, dtype=BF, device=weight.device)
+        def make():
+            t = torch.zeros(cin_cols, (cout + 63) // 64 * 64, dtype=BF, device=weight.device)
             t[:, :cout] = weight[:, :cin_cols].t()
-            self._wt[key] = t
-        return t
+            return t
+        return self.transposed(key, make)
 
     # ---- input gradient of the 3x3 / stride 2 / pad 1 convolutions without column matrices (round 4).  An input pixel
     # (2i + py, 2j + px) receives from output pixel (i + a, j + b), a <= py, b <= px, through filter tap
@@ -99,7 +111,7 @@ class ConvSideBackward:
     # 820 -> 367 (96 -> 192 @ 56), 367 -> 192 (192 -> 192 @ 28); closer to fp32 torch than the bf16 column matrix was
     # (tools/probes/dgrad_parity_probe.py).  On the large maps the two pixels of a pair share a launch (_parity_plan).
     def _parity_plan(self, key, spec):
-        # geometry only: shared by every ConvSideBackward of the process (the frozen-statistics backward builds one per step,
+        # geometry only: shared by every ConvGrad of the process (the frozen-statistics backward builds one per step,
         # and an index upload is a pageable host-to-device copy that waits for the stream to drain)
         # row pairs on the large maps (112 / 56: 543 -> 314 us, 758 -> 524, 419 -> 367), four classes on the 28 x 28 ones (192 vs 206 us)
         rows = spec.h_in >= 56
@@ -180,8 +192,7 @@ class ConvSideBackward:
         that produced this (bf16) activation -- in the parity launches' epilogues where they run, a msclip_relu_bwd pass else."""
         co, ci, kh, kw = spec.cout, spec.cin, spec.kh, spec.kw
         pix = B * spec.h_out * spec.w_out
-        K = kh * kw * ci
-        pointwise = (kh, kw, spec.stride, spec.pad) == (1, 1, 1, 0)
+        pointwise = _pointwise(spec)
         if col is None:
             if pointwise:
                 col = x_in[:pix]
@@ -195,7 +206,7 @@ class ConvSideBackward:
                 col = hip.im2col(x_in, B, spec.h_in, spec.w_in, ci, kh, kw, spec.stride, spec.pad)
 
         def to_filter(dwf):
-            return dwf[:, :K].reshape(co, kh, kw, ci).permute(0, 3, 1, 2).contiguous()
+            return dwf[:, :kh * kw * ci].reshape(co, kh, kw, ci).permute(0, 3, 1, 2).contiguous()
         if lane:
             G, db = _wgrad_async(dpre, col, pix, post=to_filter), None
         else:
@@ -224,6 +235,65 @@ class ConvSideBackward:
                 dx = self._relu_bwd(dx, relu_of)
         return G, db, dx
 
+    def _relu_bwd(self, dy, y, dy2=None):
+        out = _zbuf(dy.shape[0], dy.shape[1], dy.device)
+        hip.relu_bwd(dy, y[:dy.shape[0]], out, dy2=dy2)
+        return out
+
+    def _image_cols(self, gemm_operand=False):
+        """The image's 3 x 3 / stride 2 patch matrix (both Cin = 3 convolutions share it).  gemm_operand: it will be the X operand
+        of a forward GEMM (train-mode BatchNorm's raw convolutions), whose K axis is 64 wide; whoever asks first decides."""
+        if self.col_img is None:
+            # 27 columns padded to 32, not 64: the token-major wgrad GEMM reads it as it is (half the bytes, written and read twice)
+            self.col_img = hip.im2col(self.img, self.Bi, self.e.S, self.e.S, 3, 3, 3, 2, 1, image=True, kalign=64 if gemm_operand else 32)
+        return self.col_img
+
+    def _image_wgrad(self, dpre, lane):
+        """Weight gradient of a 3x3 / stride 2 convolution on the input image -> (G [cout, 3, 3, 3] fp32, column sums of dpre).
+        lane=True: the contraction runs on gradgemm's lane stream (G final after gradgemm.join) and no sums are formed."""
+        pix, co = self.Bi * self.e.h1 * self.e.h1, dpre.shape[1]
+
+        def to_filter(dwf):                              # (kh, kw, ci) -> [co, ci, kh, kw]
+            return dwf.reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+        # direct: one pass over dpre and the image, no patch matrix, the bias sums in the same contraction (round 5)
+        direct = hip.image_conv_wgrad_ok(self.img, dpre) and self.e.h1 <= 128
+        if lane and direct:
+            return gradgemm.on_lane(lambda: to_filter(hip.image_conv_wgrad(self.img, dpre)[0]), dpre), None
+        if lane:
+            return _wgrad_async(dpre, self._image_cols(), pix, post=lambda d: to_filter(d[:, :27])), None
+        dwf, dbias = hip.image_conv_wgrad(self.img, dpre) if direct else (_wgrad(dpre, self._image_cols(), pix)[:, :27], hip.colsum(dpre, M=pix))
+        return to_filter(dwf), dbias
+
+
+def _dpool_into(dpar, dpool, pool_w, Bi, hw, C, k):
+    """The adapter's share of dL/d(par[j]) (backward of its depthwise pooling) into dpar[0]: the first write where stage j + 1
+    handed nothing down, added to what it did else."""
+    first = dpar[0] is None
+    if first:
+        dpar[0] = _zbuf(Bi * hw * hw, C, dpool.device)
+    hip.dwpool_bwd(dpool, pool_w, dpar[0], Bi, hw, hw, C, k, accumulate=not first)
+
+
+def _stem_open(e, w, Bi, dtok):
+    """-> (dlast: bf16 gradient of last_conv's output, the grid rows of dtok; x: the map last_conv read; their row count).
+    The weight gradient, W^T and the dY GEMM that follow differ between the walks in issue order, so they stay there."""
+    dlast = hip.cast_bf16_colsum(dtok[:Bi * e.Lv], fold=False, skip_group=e.g * e.g)[0]      # (class rows skipped: one pass, no gather copy)
+    return dlast, w["stem"][-1], Bi * e.g * e.g
+
+
+class ConvSideBackward:
+    """The frozen-statistics walk: one instance per backward."""
+
+    def __init__(self, train_step):
+        self.e = train_step.eng
+        self.cg = ConvGrad(self.e)
+
+    def begin(self, img, w, Bi):
+        """Called once per backward: the model's raw parameters and the image both Cin = 3 convs read."""
+        self.sd = {k: t.detach() for k, t in self.e.model.state_dict().items()}
+        self.cg.begin(img, Bi)
+        self.w, self.Bi, self.dpar = w, Bi, [None, None]     # dpar: gradient of par[j] handed down to stage j, [shortcut path, conv1 path]
+
     def _fold_on_lane(self, grads, fold, conv_key, G, w_raw, dshift, also=None):
         """fold.grads(...) on gradgemm's lane stream, behind the weight gradient G it consumes (G comes from
         _conv_bwd(lane=True)); `also` = (fold2, key2, w_raw2) reads the centre tap of the same G (the stem's merged 1x1
@@ -248,46 +318,18 @@ class ConvSideBackward:
             return hip.colsum(dpre, M=M)
         return gradgemm.on_lane(lambda: hip.colsum(dpre, M=M), dpre)
 
-    def _relu_bwd(self, dy, y, dy2=None):
-        out = _zbuf(dy.shape[0], dy.shape[1], dy.device)
-        hip.relu_bwd(dy, y[:dy.shape[0]], out, dy2=dy2)
-        return out
-
-    def begin(self, img, w, Bi):
-        """Called once per backward: the model's raw parameters and the image patch matrix both Cin = 3 convs share."""
-        self.sd = {k: t.detach() for k, t in self.e.model.state_dict().items()}
-        self.w, self.Bi, self.img = w, Bi, img
-        self.col_img = None
-        self.dpar = [None, None]                     # gradient of par[j] handed down to stage j: [shortcut path, conv1 path]
-
-    def _image_cols(self, gemm_operand=False):
-        """The image's 3 x 3 / stride 2 patch matrix (both Cin = 3 convolutions share it).  gemm_operand: it will be the X operand
-        of a forward GEMM (train-mode BatchNorm's raw convolutions), whose K axis is 64 wide; whoever asks first decides."""
-        if self.col_img is None:
-            S = self.e.S
-            # 27 columns padded to 32, not 64: the token-major wgrad GEMM reads it as it is (half the bytes, written and read twice)
-            self.col_img = hip.im2col(self.img, self.Bi, S, S, 3, 3, 3, 2, 1, image=True, kalign=64 if gemm_operand else _image_kalign())
-        return self.col_img
-
     def _first_conv(self, grads, conv_key, bn_prefix, dpre):
         """wgrad of a 3x3 / stride 2 convolution on the input image (no input gradient)."""
-        pix = self.Bi * self.e.h1 * self.e.h1
-        co = dpre.shape[1]
-        if hip.image_conv_wgrad_ok(self.img, dpre) and self.e.h1 <= 128:
-            # one pass over dpre and the image: no patch matrix, the bias sums in the same contraction (round 5)
-            dwf, dbias = hip.image_conv_wgrad(self.img, dpre)
-        else:
-            dwf, dbias = _wgrad(dpre, self._image_cols(), pix)[:, :27], hip.colsum(dpre, M=pix)
-        G = dwf.reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()          # (kh, kw, ci) -> [co, ci, kh, kw]
+        G, dbias = self.cg._image_wgrad(dpre, lane=False)
         _Fold(self.sd, bn_prefix, 1e-5).grads(grads, conv_key, G, self.sd[conv_key].float(), dbias)
 
     # ------------------------------------------------------------------ lateral adapter j + parallel stage j
     def adapter(self, grads, j, dsum, x_pre):
-        """dsum: fp32 [Mv, D] gradient of the adapter's pre-LayerNorm sum; x_pre: the token matrix the adapter read."""
+        """dsum: fp32 [Mv, D] gradient of the adapter's pre-LayerNorm sum; x_pre: the token matrix the adapter read.
+        -> the gradient matrix to hand to msclip_adapter_dx and the depthwise filter to hand with it (the folded one)."""
         e, w, Bi, sd = self.e, self.w, self.Bi, self.sd
         a = e.adapters[j]
-        g, D, C, k, hw = e.g, e.D, a["C"], a["k"], e.par_hw[j]
-        g2 = g * g
+        g, g2, D, C, k, hw = e.g, e.g * e.g, e.D, a["C"], a["k"], e.par_hw[j]
         p = f"visual.transformer.parallel_lateral_adapter.{j}"
         # grid rows (the cls row has no top-down term): their bf16 copy and column sums from ONE pass over dsum (round 5; was a
         # gathering copy, a column-sum pass and a cast)
@@ -304,36 +346,28 @@ class ConvSideBackward:
                  sd[p + ".bottom_dw_conv.conv.weight"].float(), cs)
         # pointwise conv: T = Wp (pool_out + shift)
         ft = _Fold(sd, p + ".top2bottom_dw_conv.bn", 1e-5)
-        pool_out = w["pool"][j]
         wp = sd[p + ".top2bottom_pw_conv.conv.weight"].float()[:, :, 0, 0]        # [D, C]
-        dwp = _wgrad(dT_bf, pool_out, Bi * g2) + torch.outer(cs, ft.shift)
+        dwp = _wgrad(dT_bf, w["pool"][j], Bi * g2) + torch.outer(cs, ft.shift)
         grads[p + ".top2bottom_pw_conv.conv.weight"] = dwp.reshape(D, C, 1, 1)
         dshift = wp.t() @ cs                                                      # [C]
-        wt = self._wt.get(("pw", j))
-        if wt is None:
-            wt = self._wt[("pw", j)] = a["pw"].weight[:, :C].t().contiguous()     # [C, D] bf16
+        wt = self.cg.transposed(("pw", j), lambda: a["pw"].weight[:, :C].t().contiguous())     # [C, D] bf16
         dpool = _zbuf(Bi * g2, C, dsum.device)
         hip.gemm(dT_bf, wt, dpool)
         # depthwise kernel == stride conv + BN
         dpf = hip.dwpool_wgrad(dpool, w["par"][j], Bi, hw, hw, C, k)              # [k*k, C]
         ft.grads(grads, p + ".top2bottom_dw_conv.conv.weight", dpf.t().reshape(C, 1, k, k),
                  sd[p + ".top2bottom_dw_conv.conv.weight"].float(), dshift)
-        if self.dpar[0] is None:
-            self.dpar[0] = _zbuf(Bi * hw * hw, C, dsum.device)
-            hip.dwpool_bwd(dpool, a["pool"], self.dpar[0], Bi, hw, hw, C, k)
-        else:
-            hip.dwpool_bwd(dpool, a["pool"], self.dpar[0], Bi, hw, hw, C, k, accumulate=True)
+        _dpool_into(self.dpar, dpool, a["pool"], Bi, hw, C, k)
         self._stage(grads, j)
+        return dsum, a["dww"]
 
     def _stage(self, grads, j):
-        e, w, Bi, sd = self.e, self.w, self.Bi, self.sd
+        e, w, Bi, sd, cg = self.e, self.w, self.Bi, self.sd, self.cg
         da, db_ = self.dpar
-        out = w["par"][j]
-        dpre = self._relu_bwd(da, out, dy2=db_)
+        dpre = cg._relu_bwd(da, w["par"][j], dy2=db_)
         self.dpar = [None, None]
         if j == 0:
-            self._first_conv(grads, "visual.transformer.parallel_branch_v.0.conv.weight",
-                             "visual.transformer.parallel_branch_v.0.bn", dpre)
+            self._first_conv(grads, "visual.transformer.parallel_branch_v.0.conv.weight", "visual.transformer.parallel_branch_v.0.bn", dpre)
             return
         q = f"visual.transformer.parallel_branch_v.{j}.resnet_stage.conv_0"
         c1, c2, cr, c3 = e.par_specs[j]
@@ -344,37 +378,33 @@ class ConvSideBackward:
             # weight gradient + the fold's chain rule on the lane stream; the bias sum (main stream) feeds the latter
             dbias = self._colsum_on_lane(dpre_, Bi * spec.h_out * spec.w_out)
             self._fold_on_lane(grads, _Fold(sd, f"{q}.{bn}", 1e-6), f"{q}.{conv}.weight", G, sd[f"{q}.{conv}.weight"].float(), dbias)
-        G, _, dt2 = self._conv_bwd(("par", j, 3), c3, t2, dpre, Bi, lane=True)
+        G, _, dt2 = cg._conv_bwd(("par", j, 3), c3, t2, dpre, Bi, lane=True)
         fold("conv3", "bn3", G, dpre, c3)
-        short = self._shortcut_ok(cr)        # the shortcut's input gradient is added into conv1's below (no map of its own)
-        G, _, dsrc_a = self._conv_bwd(("par", j, "r"), cr, src, dpre, Bi, lane=True, need_dx=not short)
+        short = cg._shortcut_ok(cr)        # the shortcut's input gradient is added into conv1's below (no map of its own)
+        G, _, dsrc_a = cg._conv_bwd(("par", j, "r"), cr, src, dpre, Bi, lane=True, need_dx=not short)
         fold("residual_conv", "residual_bn", G, dpre, cr)
         if not short:
             del dpre
-        dt2 = self._relu_bwd(dt2, t2)
-        G, _, dt1 = self._conv_bwd(("par", j, 2), c2, t1, dt2, Bi, lane=True, relu_of=t1)      # (through t1's ReLU)
+        dt2 = cg._relu_bwd(dt2, t2)
+        G, _, dt1 = cg._conv_bwd(("par", j, 2), c2, t1, dt2, Bi, lane=True, relu_of=t1)      # (through t1's ReLU)
         fold("conv2", "bn2", G, dt2, c2)
         del dt2
-        G, _, dsrc_b = self._conv_bwd(("par", j, 1), c1, src, dt1, Bi, lane=True)
+        G, _, dsrc_b = cg._conv_bwd(("par", j, 1), c1, src, dt1, Bi, lane=True)
         fold("conv1", "bn1", G, dt1, c1)
         if short:
-            self._shortcut_dgrad_into(("par", j, "r"), cr, dpre, dsrc_b, Bi)
+            cg._shortcut_dgrad_into(("par", j, "r"), cr, dpre, dsrc_b, Bi)
             dsrc_a, dsrc_b = dsrc_b, None
         self.dpar = [dsrc_a, dsrc_b]
 
     # ------------------------------------------------------------------ stem
     def stem(self, grads, dtok):
         """dtok: fp32 [Mv, D] gradient of the token matrix in front of ln_pre (cls row included)."""
-        e, w, Bi, sd = self.e, self.w, self.Bi, self.sd
-        g2, D = e.g * e.g, e.D
+        e, w, Bi, sd, cg = self.e, self.w, self.Bi, self.sd, self.cg
         sp = "visual.transformer.resblocks.0"
-        dlast = hip.cast_bf16_colsum(dtok[:Bi * e.Lv], fold=False, skip_group=g2)[0]     # the grid rows (class rows skipped), one pass, no gather copy
-        x = w["stem"][-1]
-        grads[sp + ".last_conv.weight"] = _wgrad(dlast, x[:Bi * g2], Bi * g2).reshape(D, x.shape[1], 1, 1)
-        wt = self._wt.get("last")
-        if wt is None:
-            wt = self._wt["last"] = e.w_last.t().contiguous()                    # [Cin, D]
-        dy = _zbuf(Bi * g2, x.shape[1], dtok.device)
+        dlast, x, n = _stem_open(e, w, Bi, dtok)
+        grads[sp + ".last_conv.weight"] = _wgrad(dlast, x[:n], n).reshape(e.D, x.shape[1], 1, 1)
+        wt = cg.transposed("last", lambda: e.w_last.t().contiguous())           # [Cin, D]
+        dy = _zbuf(n, x.shape[1], dtok.device)
         hip.gemm(dlast, wt, dy)
         for i in reversed(range(len(e.stem_specs))):
             spec = e.stem_specs[i]
@@ -382,17 +412,16 @@ class ConvSideBackward:
             x_in = w["stem"][i - 1] if i else w["S1"]
             # dy arrives through the ReLU of this stage's output: from the previous iteration's convolution backward
             # (relu_of = its input map = this stage's output), or the pass below for the last stage
-            dpre = self._relu_bwd(dy, w["stem"][i]) if i == len(e.stem_specs) - 1 else dy
-            G, _, dy = self._conv_bwd(("stem", i), spec, x_in, dpre, Bi, lane=True, relu_of=x_in)
+            dpre = cg._relu_bwd(dy, w["stem"][i]) if i == len(e.stem_specs) - 1 else dy
+            G, _, dy = cg._conv_bwd(("stem", i), spec, x_in, dpre, Bi, lane=True, relu_of=x_in)
             dbias = self._colsum_on_lane(dpre, Bi * spec.h_out * spec.w_out)
             self._fold_on_lane(grads, _Fold(sd, q + ".bn1", 1e-5), q + ".conv1.weight", G, sd[q + ".conv1.weight"].float(), dbias,
                                also=(_Fold(sd, q + ".downsample.1", 1e-5), q + ".downsample.0.weight",
                                      sd[q + ".downsample.0.weight"].float()))
         self._first_conv(grads, sp + ".conv1.weight", sp + ".bn1", dy)          # (dy already went through S1's ReLU: relu_of above)
-        self.col_img = None
+        cg.col_img = None
 
 
-# ----------------------------------------------------------------------------------------------------------------------
 # Train-mode BatchNorm (per-GPU batch statistics): what nn.BatchNorm2d does in train() (M.py:1825-1861, 1920-1936).
 # Forward: every convolution runs with its RAW weights (no fold), the batch mean / biased variance of its output are
 # reduced on the GPU (msclip_bn_stats), normalise + affine (+ residual, ReLU) is one element-wise pass (msclip_bn_apply),
@@ -400,10 +429,6 @@ class ConvSideBackward:
 # the gradient of the raw convolution output (msclip_bn_bwd_reduce / _dx), then the same GEMM-based convolution backward
 # as above on the raw weights (no fold chain rule).  The stem's 3x3 and its 1x1 shortcut are separate convolutions here:
 # their two BatchNorms see different statistics, the centre-tap merge only holds for frozen statistics.
-# ----------------------------------------------------------------------------------------------------------------------
-from . import packing as P
-
-
 class _RawSpecs:
     """Raw-weight ConvSpecs (geometry and chunk tables built once; weights refreshed from the module every step)."""
 
@@ -474,7 +499,6 @@ class _RawSpecs:
         return t.finalize()
 
     def _refresh_eager(self, sd):
-        e = self.e
         for sp_, key in self.items:
             # [Cout, Cin, KH, KW] fp32 -> the spec's [Cout, Kpad] bf16 matrix in (kh, kw, ci) order: ONE strided, converting copy
             # into its first K columns (the pad columns stay zero) instead of permute / pad / cast / copy
@@ -502,17 +526,21 @@ class _RawSpecs:
         self.sd = sd
 
 
+# What a BatchNorm's forward keeps for its backward: x [rows, C] (the raw map, or xhat with mean 0 / rstd 1 / gamma := gamma rstd),
+# the statistics over `rows` rows.  tokens: set for the adapter's view form, where x still holds the class rows (L tokens per sample).
+_SavedBN = namedtuple("_SavedBN", "x mean rstd gamma rows tokens", defaults=(None,))
+
+
 class ConvSideBatchNorm:
     """Forward and backward of the conv side with train-mode BatchNorm.  One instance per TrainStep."""
     MOMENTUM = 0.1
 
     def __init__(self, train_step):
-        self.ts = train_step
         self.e = train_step.eng
         self.raw = _RawSpecs(self.e)
         self._two_pass = {}                              # conv shape -> does msclip_gemm take it in its BatchNorm modes
         self._zeros = {}                                 # read-only zero operands of the adapters' raw depthwise pass
-        self.bw = ConvSideBackward(train_step)           # its generic pieces (_conv_bwd, _relu_bwd, patch matrix) are reused
+        self.cg = ConvGrad(self.e)
 
     # ------------------------------------------------------------------ forward
     def _bn(self, x_raw, prefix, eps, out, M, relu=False, resid=None):
@@ -520,7 +548,7 @@ class ConvSideBatchNorm:
         g = sd[prefix + ".weight"]
         mean, var, rstd, scale, shift = hip.bn_stats(x_raw, M, gamma=g, beta=sd[prefix + ".bias"], eps=eps)
         hip.bn_apply(x_raw, scale, shift, out, M, relu=relu, resid=resid)
-        self.saved[prefix] = (x_raw, mean, rstd, g, M)
+        self.saved[prefix] = _SavedBN(x_raw, mean, rstd, g, M)
         self.stats[prefix] = (mean, var, M)
         return out
 
@@ -528,8 +556,7 @@ class ConvSideBatchNorm:
         """Does msclip_gemm run this convolution in its BatchNorm modes (the streaming kernel's shapes)?  Asked once per shape."""
         if not options.TRAIN.bn_two_pass:
             return False
-        pointwise = spec.kh == 1 and spec.kw == 1 and spec.stride == 1 and spec.pad == 0
-        key = (spec.cin, spec.cout, spec.weight.shape[1], M, None if pointwise else spec.geometry())
+        key = (spec.cin, spec.cout, spec.weight.shape[1], M, None if _pointwise(spec) else spec.geometry())
         if key not in self._two_pass:
             self._two_pass[key] = hip.gemm_bn_two_pass_ok(spec.cin, spec.cout, spec.weight.shape[1], M, conv=key[4])
         return self._two_pass[key]
@@ -540,13 +567,13 @@ class ConvSideBatchNorm:
         (options.TRAIN.bn_two_pass) --, the others as raw fp32 map + statistics pass + normalise pass.  two_pass: the caller's choice
         for BatchNorms whose backward shares one pass (both sides of a residual block must keep the same kind of map)."""
         e, Bi = self.e, self.Bi
-        pointwise = spec.kh == 1 and spec.kw == 1 and spec.stride == 1 and spec.pad == 0
-        kw = dict(M=M, N=spec.cout, ldx=spec.cin) if pointwise else dict(M=M, N=spec.cout, conv=spec.geometry(), ktab=spec.ktab)
+        kw = dict(M=M, N=spec.cout, ldx=spec.cin) if _pointwise(spec) else dict(M=M, N=spec.cout, conv=spec.geometry(), ktab=spec.ktab)
         if two_pass is None:
             two_pass = self._two_pass_ok(spec, M)
         if two_pass:                                         # (raw specs carry a zero bias)
             assert out.stride(0) == spec.cout and (resid is None or resid.stride(0) == spec.cout)
-            part = self._part_rows(spec.cout, e.dev)
+            # zeroed [2048, 2 N] partial-sum rows of the statistics launch (a wave per row; rows of waves that do not exist stay zero)
+            part = torch.zeros(2048, 2 * spec.cout, dtype=F32, device=e.dev)
             hip.gemm(x, spec.weight, part, bn_stats_part=part, **kw)
             sd = self.raw.sd
             g = sd[prefix + ".weight"]
@@ -557,29 +584,22 @@ class ConvSideBatchNorm:
             xh = _zbuf(out.shape[0], spec.cout, e.dev)
             hip.gemm(x, spec.weight, out, out2=xh, bn_consts=o, act=hip.ACT_RELU if relu else hip.ACT_NONE, resid=resid,
                      resid_kind=hip.RESID_BF16 if resid is not None else hip.RESID_NONE, **kw)
-            zero, one = hip._bn_unit(spec.cout, e.dev)[1], hip._bn_unit(spec.cout, e.dev)[0]
-            self.saved[prefix] = (xh, zero, one, scale, M)
+            one, zero = hip._bn_unit(spec.cout, e.dev)
+            self.saved[prefix] = _SavedBN(xh, zero, one, scale, M)
             self.stats[prefix] = (mean, var, M)
             return out
         r = torch.empty(M, spec.cout, dtype=F32, device=e.dev)       # raw conv outputs stay fp32 until normalised
         e._conv(x, spec, r, Bi)
         return self._bn(r, prefix, eps, out, M, relu=relu, resid=resid)
 
-    def _part_rows(self, N, dev):
-        """Zeroed [2048, 2 N] partial-sum rows of a statistics launch (a wave per row; rows of waves that do not exist stay zero)."""
-        return torch.zeros(2048, 2 * N, dtype=F32, device=dev)
-
     def begin(self, img, w, Bi):
         self.raw.refresh()
         self.saved, self.stats = {}, {}
-        self.w, self.Bi, self.img = w, Bi, img
-        self.bw.begin(img, w, Bi)
-        self.bw.sd = self.raw.sd
-        self.bw._wt = {}                                 # transposed dgrad weights of the previous step are stale
+        self.cg.begin(img, Bi)
+        self.w, self.Bi, self.img, self.dpar = w, Bi, img, [None, None]      # (dpar: as in ConvSideBackward)
 
     def front(self):
-        """conv1 / parallel stage 0 (both from one patch matrix of the image) and the four stem stages -> w["S1"], w["P0"],
-        w["stem"][i]."""
+        """conv1 / parallel stage 0 (both from one patch matrix of the image) and the four stem stages -> w["S1"], w["P0"], w["stem"][i]."""
         e, w, Bi = self.e, self.w, self.Bi
         sp = "visual.transformer.resblocks.0"
         pix = Bi * e.h1 * e.h1
@@ -591,18 +611,17 @@ class ConvSideBatchNorm:
             xh = [_zbuf(pix, 48, e.dev) for _ in heads]
             res = hip.stem_conv_dual_bn(self.img, self.raw.w_dual, [(sd[p + ".weight"], sd[p + ".bias"]) for _, p, _ in heads],
                                         heads[0][2], heads[1][2], xh[0], xh[1], eps=1e-5)
-            zero, one = hip._bn_unit(48, e.dev)[1], hip._bn_unit(48, e.dev)[0]
+            one, zero = hip._bn_unit(48, e.dev)
             for (_, prefix, _), x, (mean, var, rstd, scale, shift) in zip(heads, xh, res):
-                self.saved[prefix] = (x, zero, one, scale, pix)
+                self.saved[prefix] = _SavedBN(x, zero, one, scale, pix)
                 self.stats[prefix] = (mean, var, pix)
-            raws = []
-            heads = ()
+            raws, heads = [], ()
         elif self.raw.w_dual is not None and e.S % 2 == 0:
             # both raw convolutions from ONE pass over the image (round 5): no patch matrix, no two GEMMs over it
             raws = [torch.empty(pix, 48, dtype=F32, device=e.dev) for _ in heads]
             hip.stem_conv_dual_raw(self.img, self.raw.w_dual, raws[0], raws[1])
         else:
-            col = self.bw._image_cols(gemm_operand=True)
+            col = self.cg._image_cols(gemm_operand=True)
             raws = []
             for wt, _, _ in heads:
                 r = torch.empty(pix, wt.shape[0], dtype=F32, device=e.dev)  # raw conv outputs stay fp32 until normalised
@@ -656,32 +675,31 @@ class ConvSideBatchNorm:
         p = f"visual.transformer.parallel_lateral_adapter.{j}.bottom_dw_conv.bn"
         sd = self.raw.sd
         gam = sd[p + ".weight"]
+        n = Bi * g * g
         raw_full = torch.empty(Bi * L, D, dtype=F32, device=e.dev)
-        if options.TRAIN.adapter_bn_views:
+        views = options.TRAIN.adapter_bn_views
+
+        def zeros():
+            return torch.zeros(n, D, dtype=F32, device=e.dev), torch.zeros(D, dtype=F32, device=e.dev)
+        if views and (n, D) not in self._zeros:
+            self._zeros[(n, D)] = zeros()                                # (read-only: kept)
+        zero_t, zero_b = self._zeros[(n, D)] if views else zeros()
+        hip.adapter_sum(X, zero_t, self.raw.dww[j], zero_b, raw_full, Bi, L, g, e.usecls)
+        if views:
             # no copy of the grid rows and no fill: a sample is ONE row of L * D columns, the statistics are taken per (token, channel)
             # column and the class token's columns are left out of the fold over tokens
-            key = (Bi * g * g, D)
-            if key not in self._zeros:
-                self._zeros[key] = (torch.zeros(Bi * g * g, D, dtype=F32, device=e.dev), torch.zeros(D, dtype=F32, device=e.dev))
-            zero_t, zero_b = self._zeros[key]                            # (read-only)
-            hip.adapter_sum(X, zero_t, self.raw.dww[j], zero_b, raw_full, Bi, L, g, e.usecls)
             part = hip.bn_stats_partials(raw_full.view(Bi, L * D))       # [1][2][L * D]
             sums = part.view(2, L, D)[:, 1:].sum(1)
             o = torch.empty(5, D, dtype=F32, device=e.dev)
-            hip.bn_finish(sums, D, Bi * g * g, gam, sd[p + ".bias"], 1e-5, o)
+            hip.bn_finish(sums, D, n, gam, sd[p + ".bias"], 1e-5, o)
             mean, var, rstd, scale, shift = (o[k] for k in range(5))
-            hip.adapter_sum(X, t, (self.raw.dww[j] * scale).contiguous(), shift, out, Bi, L, g, e.usecls)
-            self.saved[p] = (raw_full, mean, rstd, gam, Bi * g * g, L)   # (6 entries: the map still holds the class rows)
-            self.stats[p] = (mean, var, Bi * g * g)
-            return
-        zero_t = torch.zeros(Bi * g * g, D, dtype=F32, device=e.dev)
-        zero_b = torch.zeros(D, dtype=F32, device=e.dev)
-        hip.adapter_sum(X, zero_t, self.raw.dww[j], zero_b, raw_full, Bi, L, g, e.usecls)
-        graw = raw_full.view(Bi, L, D)[:, 1:].reshape(Bi * g * g, D)
-        mean, var, rstd, scale, shift = hip.bn_stats(graw, gamma=gam, beta=sd[p + ".bias"], eps=1e-5)
+            x, tokens = raw_full, L                                      # (the map still holds the class rows)
+        else:
+            x, tokens = raw_full.view(Bi, L, D)[:, 1:].reshape(n, D), None
+            mean, var, rstd, scale, shift = hip.bn_stats(x, gamma=gam, beta=sd[p + ".bias"], eps=1e-5)
         hip.adapter_sum(X, t, (self.raw.dww[j] * scale).contiguous(), shift, out, Bi, L, g, e.usecls)
-        self.saved[p] = (graw, mean, rstd, gam, Bi * g * g)
-        self.stats[p] = (mean, var, Bi * g * g)
+        self.saved[p] = _SavedBN(x, mean, rstd, gam, n, tokens)
+        self.stats[p] = (mean, var, n)
 
     def record_stream(self, stream, skip=()):
         """Tell the caching allocator that `stream` reads what the forward saved for the backward (self.saved) and for the running
@@ -720,9 +738,9 @@ class ConvSideBatchNorm:
     def _bn_bwd(self, grads, prefix, dy, _plain=False):
         if not _plain and options.TRAIN.bn_bwd_fused and dy.dtype == BF:
             return self._bn_bwd_masked(grads, [prefix], dy)[0]       # (the 4-columns-per-thread passes; falls back to here)
-        x_raw, mean, rstd, gam, M = self.saved[prefix]
-        dx = torch.empty_like(dy) if dy.dtype == F32 else _zbuf(x_raw.shape[0], x_raw.shape[1], x_raw.device)
-        dg, db = hip.bn_bwd(dy, x_raw, mean, rstd, gam, dx, M)
+        sv = self.saved[prefix]
+        dx = torch.empty_like(dy) if dy.dtype == F32 else _zbuf(sv.x.shape[0], sv.x.shape[1], sv.x.device)
+        dg, db = hip.bn_bwd(dy, sv.x, sv.mean, sv.rstd, sv.gamma, dx, sv.rows)
         grads[prefix + ".weight"], grads[prefix + ".bias"] = dg, db
         return dx
 
@@ -730,53 +748,43 @@ class ConvSideBatchNorm:
         """The BatchNorms `prefixes` (one, or a residual block's two) behind d = (dy [+ dy2]) * (y > 0): one fused reduce + one fused
         dx pass (msclip_bn_bwd_fused) where the shapes allow, the ReLU pass + a pass pair per BatchNorm else.  -> [dx per prefix]"""
         saved = [self.saved[p] for p in prefixes]
-        M = saved[0][4]
-        if options.TRAIN.bn_bwd_fused and dy.dtype == BF and all(sv[4] == M for sv in saved):
-            dxs = [_zbuf(sv[0].shape[0], sv[0].shape[1], sv[0].device) for sv in saved]
-            sides = [(sv[0], sv[1], sv[2], sv[3], dx) for sv, dx in zip(saved, dxs)]
-        else:
-            sides = None
-        if sides is not None and hip.bn_bwd_fused_ok(dy, sides, y, dy2, M):
+        M = saved[0].rows
+        fused = options.TRAIN.bn_bwd_fused and dy.dtype == BF and all(sv.rows == M for sv in saved)
+        if fused:
+            dxs = [_zbuf(sv.x.shape[0], sv.x.shape[1], sv.x.device) for sv in saved]
+            sides = [(sv.x, sv.mean, sv.rstd, sv.gamma, dx) for sv, dx in zip(saved, dxs)]
+        if fused and hip.bn_bwd_fused_ok(dy, sides, y, dy2, M):
             res = hip.bn_bwd_fused(dy, sides, y=y, dy2=dy2, M=M)
             for p, (dg, db) in zip(prefixes, res):
                 grads[p + ".weight"], grads[p + ".bias"] = dg, db
             return dxs
-        dpre = self.bw._relu_bwd(dy, y, dy2=dy2) if y is not None else dy
+        dpre = self.cg._relu_bwd(dy, y, dy2=dy2) if y is not None else dy
         assert y is not None or dy2 is None
         return [self._bn_bwd(grads, p, dpre, _plain=True) for p in prefixes]
 
     def _conv(self, grads, key, spec, wkey, x_in, draw, need_dx=True, relu_of=None):
-        G, _, dx = self.bw._conv_bwd(key, spec, x_in, draw, self.Bi, need_dx=need_dx, lane=True, relu_of=relu_of)
+        G, _, dx = self.cg._conv_bwd(key, spec, x_in, draw, self.Bi, need_dx=need_dx, lane=True, relu_of=relu_of)
         grads[wkey] = G                                  # final after gradgemm.join (end of the backward / bucket flush)
         return dx
 
     def _first(self, grads, wkey, prefix, dy, y=None, dy2=None):
         draw, = self._bn_bwd_masked(grads, [prefix], dy, y=y, dy2=dy2)
-        pix = self.Bi * self.e.h1 * self.e.h1
-        co = draw.shape[1]
-        if hip.image_conv_wgrad_ok(self.img, draw) and self.e.h1 <= 128:
-            # one pass over draw and the image on the lane: no patch matrix (the bias column is not needed: dbeta comes from the BatchNorm backward)
-            grads[wkey] = gradgemm.on_lane(
-                lambda: hip.image_conv_wgrad(self.img, draw)[0].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous(), draw)
-        else:
-            grads[wkey] = _wgrad_async(draw, self.bw._image_cols(), pix,
-                                       post=lambda d: d[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous())
+        grads[wkey], _ = self.cg._image_wgrad(draw, lane=True)
 
     def adapter(self, grads, j, dsum, x_pre):
         """-> the gradient matrix to hand to msclip_adapter_dx together with the RAW depthwise filter."""
         e, w, Bi = self.e, self.w, self.Bi
         a = e.adapters[j]
-        g, D, C, k, hw, L = e.g, e.D, a["C"], a["k"], e.par_hw[j], e.Lv
-        g2 = g * g
+        g, g2, D, C, k, hw, L = e.g, e.g * e.g, e.D, a["C"], a["k"], e.par_hw[j], e.Lv
         p = f"visual.transformer.parallel_lateral_adapter.{j}"
         sv = self.saved[p + ".bottom_dw_conv.bn"]
-        if len(sv) == 6:
+        if sv.tokens is not None:
             # (options.TRAIN.adapter_bn_views) the BatchNorm backward over whole samples as rows of L * D columns: the class token's
             # columns get mean 0 / rstd 1 / gamma 1 and no share of the sums, i.e. dx = dy there -- one pass writes the whole matrix
             # that msclip_adapter_dx reads; no gather of the grid rows, no clone, no scatter back
-            x_full, mean, rstd, gam, n, _ = sv
             dfull = torch.empty_like(dsum)
-            dg, db = hip.bn_bwd_token_columns(dsum.view(Bi, L * D), x_full.view(Bi, L * D), mean, rstd, gam, dfull.view(Bi, L * D), L, n)
+            dg, db = hip.bn_bwd_token_columns(dsum.view(Bi, L * D), sv.x.view(Bi, L * D), sv.mean, sv.rstd, sv.gamma,
+                                              dfull.view(Bi, L * D), L, sv.rows)
             grads[p + ".bottom_dw_conv.bn.weight"], grads[p + ".bottom_dw_conv.bn.bias"] = dg, db
             dT_bf = hip.cast_bf16_colsum(dsum, fold=False, skip_group=g2)[0]
         else:
@@ -788,26 +796,20 @@ class ConvSideBatchNorm:
             dT_bf = hip.cast_bf16(dT)
         grads[p + ".bottom_dw_conv.conv.weight"] = hip.dw3x3_wgrad(dfull, x_pre, Bi, L, g).t().reshape(D, 1, 3, 3)
         # top-down: T = Wp . BN(dwpool(par[j]))
-        pw = self.raw.pw[j]
-        grads[p + ".top2bottom_pw_conv.conv.weight"] = _wgrad_async(dT_bf, w["pool"][j], Bi * g2,
-                                                                    post=lambda d: d.reshape(D, C, 1, 1))
-        wt = pw.weight[:, :C].t().contiguous()
+        grads[p + ".top2bottom_pw_conv.conv.weight"] = _wgrad_async(dT_bf, w["pool"][j], Bi * g2, post=lambda d: d.reshape(D, C, 1, 1))
+        wt = self.raw.pw[j].weight[:, :C].t().contiguous()
         dt = _zbuf(Bi * g2, C, e.dev)
         hip.gemm(dT_bf, wt, dt)
         dpool = self._bn_bwd(grads, p + ".top2bottom_dw_conv.bn", dt)
         grads[p + ".top2bottom_dw_conv.conv.weight"] = hip.dwpool_wgrad(dpool, w["par"][j], Bi, hw, hw, C, k).t().reshape(C, 1, k, k)
-        if self.bw.dpar[0] is None:
-            self.bw.dpar[0] = _zbuf(Bi * hw * hw, C, e.dev)
-            hip.dwpool_bwd(dpool, self.raw.pool[j], self.bw.dpar[0], Bi, hw, hw, C, k)
-        else:
-            hip.dwpool_bwd(dpool, self.raw.pool[j], self.bw.dpar[0], Bi, hw, hw, C, k, accumulate=True)
+        _dpool_into(self.dpar, dpool, self.raw.pool[j], Bi, hw, C, k)
         self._stage_bwd(grads, j)
         return dfull, self.raw.dww[j]
 
     def _stage_bwd(self, grads, j):
-        e, w = self.e, self.w
-        da, db_ = self.bw.dpar
-        self.bw.dpar = [None, None]
+        w = self.w
+        da, db_ = self.dpar
+        self.dpar = [None, None]
         if j == 0:
             self._first(grads, "visual.transformer.parallel_branch_v.0.conv.weight", "visual.transformer.parallel_branch_v.0.bn", da,
                         y=w["par"][j], dy2=db_)
@@ -818,7 +820,7 @@ class ConvSideBatchNorm:
         d3, dr = self._bn_bwd_masked(grads, [q + ".bn3", q + ".residual_bn"], da, y=w["par"][j], dy2=db_)
         del da, db_
         dt2 = self._conv(grads, ("par", j, 3), c3, q + ".conv3.weight", t2, d3)
-        short = self.bw._shortcut_ok(cr)     # the shortcut's input gradient is added into conv1's below (no map of its own)
+        short = self.cg._shortcut_ok(cr)     # the shortcut's input gradient is added into conv1's below (no map of its own)
         dsrc_a = self._conv(grads, ("par", j, "r"), cr, q + ".residual_conv.weight", src, dr, need_dx=not short)
         del d3
         if not short:
@@ -829,19 +831,17 @@ class ConvSideBatchNorm:
         d1 = self._bn_bwd(grads, q + ".bn1", dt1)
         dsrc_b = self._conv(grads, ("par", j, 1), c1, q + ".conv1.weight", src, d1)
         if short:
-            self.bw._shortcut_dgrad_into(("par", j, "r"), cr, dr, dsrc_b, self.Bi)
+            self.cg._shortcut_dgrad_into(("par", j, "r"), cr, dr, dsrc_b, self.Bi)
             dsrc_a, dsrc_b = dsrc_b, None
-        self.bw.dpar = [dsrc_a, dsrc_b]
+        self.dpar = [dsrc_a, dsrc_b]
 
     def stem(self, grads, dtok):
         e, w, Bi = self.e, self.w, self.Bi
-        g2, D = e.g * e.g, e.D
         sp = "visual.transformer.resblocks.0"
-        dlast = hip.cast_bf16_colsum(dtok[:Bi * e.Lv], fold=False, skip_group=g2)[0]     # the grid rows (class rows skipped), one pass, no gather copy
-        x = w["stem"][-1]
+        dlast, x, n = _stem_open(e, w, Bi, dtok)
         cin = x.shape[1]
-        grads[sp + ".last_conv.weight"] = _wgrad_async(dlast, x[:Bi * g2], Bi * g2, post=lambda d: d.reshape(D, cin, 1, 1))
-        dy = _zbuf(Bi * g2, x.shape[1], e.dev)
+        grads[sp + ".last_conv.weight"] = _wgrad_async(dlast, x[:n], n, post=lambda d: d.reshape(e.D, cin, 1, 1))
+        dy = _zbuf(n, cin, e.dev)
         hip.gemm(dlast, e.w_last.t().contiguous(), dy)
         dy2 = None
         for i in reversed(range(len(self.raw.stem))):
@@ -849,12 +849,12 @@ class ConvSideBatchNorm:
             x_in = w["stem"][i - 1] if i else w["S1"]
             dm, ds = self._bn_bwd_masked(grads, [q + ".bn1", q + ".downsample.1"], dy, y=w["stem"][i], dy2=dy2)
             dy = self._conv(grads, ("stem", i, "m"), main, q + ".conv1.weight", x_in, dm)
-            if self.bw._shortcut_ok(short):              # the 1x1 / stride-2 shortcut's input gradient: added into the main path's map
+            if self.cg._shortcut_ok(short):              # the 1x1 / stride-2 shortcut's input gradient: added into the main path's map
                 self._conv(grads, ("stem", i, "s"), short, q + ".downsample.0.weight", x_in, ds, need_dx=False)
-                self.bw._shortcut_dgrad_into(("stem", i, "s"), short, ds, dy, Bi)
+                self.cg._shortcut_dgrad_into(("stem", i, "s"), short, ds, dy, Bi)
                 dy2 = None
             else:
                 dy2 = self._conv(grads, ("stem", i, "s"), short, q + ".downsample.0.weight", x_in, ds)
         self._first(grads, sp + ".conv1.weight", sp + ".bn1", dy, y=w["S1"], dy2=dy2)
-        self.bw.col_img = None
+        self.cg.col_img = None
         self.saved = {}                                  # the raw maps (several GB at batch 512) are not kept between steps

@@ -1139,7 +1139,7 @@ def test_train_synthetic_script(gpu_device):
 @pytest.mark.parametrize("ci,co,h,B", [(48, 48, 28, 3), (48, 96, 56, 2), (96, 192, 28, 3), (192, 192, 28, 2), (384, 384, 14, 2), (48, 48, 30, 2)])
 def test_conv_input_gradient_by_parity_classes(gpu_device, monkeypatch, ci, co, h, B):
     """dX of a 3x3 / stride 2 / pad 1 convolution as four stride-1 implicit-GEMM launches over dY, one per input-pixel parity
-    class, scattered straight into dX (train_conv.ConvSideBackward._dgrad_parity, round 4): against fp32 conv_transpose2d of the
+    class, scattered straight into dX (train_conv.ConvGrad._dgrad_parity, round 4): against fp32 conv_transpose2d of the
     same bf16 operands, against the column-matrix path (dcol GEMM + msclip_col2im), every dX row written; 14 x 14 maps keep the
     column-matrix path."""
     from msclip_amd import packing as P, train_conv as TC
@@ -1152,8 +1152,7 @@ def test_conv_input_gradient_by_parity_classes(gpu_device, monkeypatch, ci, co, 
     dpre.copy_((torch.randn(pix, co, generator=g) * 0.5).to(BF))
     x_in = TC._zbuf(B * h * h, ci, "cuda")
     x_in.copy_(torch.randn(B * h * h, ci, generator=g).to(BF))
-    bw = object.__new__(TC.ConvSideBackward)
-    bw._wt, bw._pplan = {}, TC._PARITY_PLANS
+    bw = TC.ConvGrad(None)                                               # (no engine: nothing here touches the input image)
     assert bw._parity_ok(spec) == (h >= 28)
     col = hip.im2col(x_in, B, h, h, ci, 3, 3, 2, 1)
     G, db, dx = bw._conv_bwd("t", spec, x_in, dpre, B, col=col)

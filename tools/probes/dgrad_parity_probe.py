@@ -1,4 +1,4 @@
-"""Parity-class dgrad of the 3x3 / stride-2 convolutions (train_conv.ConvSideBackward._dgrad_parity) against fp32 torch and against
+"""Parity-class dgrad of the 3x3 / stride-2 convolutions (train_conv.ConvGrad._dgrad_parity) against fp32 torch and against
 the column-matrix path (dcol GEMM + col2im), per geometry of the B/32 conv side at batch 512."""
 import os
 import sys
@@ -10,8 +10,7 @@ from msclip_amd import hip, packing as P, train_conv as TC                 # noq
 BF = torch.bfloat16
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 g = torch.Generator().manual_seed(3)
-bw = object.__new__(TC.ConvSideBackward)
-bw._wt, bw._pplan = {}, TC._PARITY_PLANS
+bw = TC.ConvGrad(None)                                                     # (no engine: nothing here touches the input image)
 for name, ci, co, h in [("par1.conv2", 48, 48, 112), ("stem0.conv1", 48, 96, 112), ("par2.conv2", 96, 96, 56), ("stem1.conv1", 96, 192, 56),
                         ("par3.conv2", 192, 192, 28), ("stem2.conv1", 192, 384, 28)]:
     w = torch.randn(co, ci, 3, 3, generator=g) * (2.0 / (9 * ci)) ** 0.5

@@ -6,12 +6,15 @@ leave every part equal):
 Per case: forward() + backward() (accumulate() in its case) on its SECOND call, after a warm-up that allocates workspaces and
 lazy tables, under tests/stream_order.Recorder, as tests/test_gpu_stream_order.py::_traced does.  No optimizer step: the token
 embedding's gradient is an atomic scatter-add, and an update from it would make the traced call's weights differ from run to
-run.  Synthetic weights and inputs, fixed seeds, plan=False.  One JSON file, per case:
+run.  The "reweighted" kind halves every conv-side parameter in place between the warm-up and the traced call instead (exact, and
+the engine repacks): a transposed or packed operand that outlives its weights shows in the hashes.  Synthetic weights and
+inputs, fixed seeds, plan=False.  One JSON file, per case:
   "order"   the issue-order record: every access as [name, stream role, reads, writes] with reads / writes as [argument, bytes],
             every alloc / record_stream / record / wait_event / wait_stream / sync in place; streams and events as indices by
             first appearance, sizes instead of addresses;
   "counts"  Trace.counts() and the number of events;
   "sha256"  of the loss's bytes and of every returned gradient's bytes, by key;
+  "buffers" (bn="batch" only) sha256 of every BatchNorm running_mean / running_var / num_batches_tracked after the traced call;
   "peak"    torch.cuda.max_memory_allocated() of the traced call; "peak_above_base": less what was allocated when it began.
 GPU only; reads nothing outside the repository; not a test."""
 import argparse
@@ -32,7 +35,7 @@ from msclip_amd import options, synth, train             # noqa: E402
 from msclip_amd.clip_openai_pe_res_v1 import get_clip_model      # noqa: E402
 from msclip_amd.config import named_config               # noqa: E402
 
-B32, L14 = "b32-yfcc-msclips", "l14-fp8-msclips"
+B32, B16, L14 = "b32-yfcc-msclips", "b16-yfcc-msclips", "l14-fp8-msclips"
 #        name: (model, extra config, TrainStep bn, batch, EngineOptions fields, TrainOptions fields, kind)
 CASES = {"frozen": (B32, [], "frozen", 4, {}, {}, "step"),
          "batch": (B32, [], "batch", 4, {}, {}, "step"),
@@ -41,7 +44,20 @@ CASES = {"frozen": (B32, [], "frozen", 4, {}, {}, "step"),
          "accumulate": (B32, [], "frozen", 4, {}, {}, "accumulate"),
          "l14": (L14, [], "frozen", 4, {}, {}, "step"),
          "rows256": (B32, [], "frozen", 256, dict(text_pack=False), {}, "step"),
-         "wgrad_sync": (B32, [], "frozen", 4, {}, dict(wgrad_sync=True), "step")}
+         "wgrad_sync": (B32, [], "frozen", 4, {}, dict(wgrad_sync=True), "step"),
+         # the conv side (train_conv.py) beyond its defaults: every fallback of the train-mode walk, the column-matrix / main-stream
+         # forms of the frozen one, no lane, the other map sizes (parity-plan thresholds), chunks, weights that changed
+         "batch_plain": (B32, [], "batch", 4, {},
+                         dict(bn_two_pass=False, bn_bwd_fused=False, adapter_bn_views=False, raw_pack_table=False), "step"),
+         "frozen_col2im": (B32, [], "frozen", 4, {}, dict(dgrad_col2im=True, im2col_main=True, colsum_main=True), "step"),
+         "batch_wgrad_sync": (B32, [], "batch", 4, {}, dict(wgrad_sync=True), "step"),
+         "b16_frozen": (B16, [], "frozen", 4, {}, {}, "step"),
+         "b16_batch": (B16, [], "batch", 4, {}, {}, "step"),
+         "batch_accumulate": (B32, [], "batch", 4, {}, {}, "accumulate"),
+         "frozen_reweighted": (B32, [], "frozen", 4, {}, {}, "reweighted"),
+         "batch_reweighted": (B32, [], "batch", 4, {}, {}, "reweighted")}
+CONV_SIDE = ("visual.transformer.resblocks.0.", "visual.transformer.parallel_branch_v.", "visual.transformer.parallel_lateral_adapter.")
+BN_BUFFERS = (".running_mean", ".running_var", ".num_batches_tracked")
 
 
 def sha(t):
@@ -108,6 +124,11 @@ def run_case(name):
             loss = ts.forward(img, tok, drop_masks=masks)
             return loss, ts.backward()
         once()
+        if kind == "reweighted":
+            with torch.no_grad():
+                for k, p in m.named_parameters():
+                    if k.startswith(CONV_SIDE):
+                        p.mul_(0.5)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
@@ -120,8 +141,11 @@ def run_case(name):
     hashes = {"loss": sha(loss)}
     hashes.update({k: sha(g) for k, g in sorted(grads.items())})
     rec_order = order(rec.trace)
-    return dict(order=rec_order, counts=dict(rec.trace.counts(), records=len(rec_order)), sha256=hashes, peak=peak,
-                peak_above_base=peak - base)
+    out = dict(order=rec_order, counts=dict(rec.trace.counts(), records=len(rec_order)), sha256=hashes, peak=peak,
+               peak_above_base=peak - base)
+    if bn == "batch":
+        out["buffers"] = {k: sha(b) for k, b in sorted(m.named_buffers()) if k.endswith(BN_BUFFERS)}
+    return out
 
 
 def main():
