@@ -6,6 +6,8 @@
   (torchvision is not installed; the reference uses lib/config/default.py:84-85 statistics)   (zero_shot.py:202-207)
 * logits = 100 * f_img @ W, top-k accuracy                                (zero_shot.py:265-266, 149-163)
 * ImageFolder layout val/<wnid>/*.JPEG, class index = sorted directory names (DATASET/DATA.md:5-14)
+* TEST.METRIC mean-per-class, 11point_mAP, roc_auc: the logits of the whole set in one device buffer, the metric behind the
+  last batch (msclip_amd/metrics.py); VOC2007 and Hateful Memes arrive as `items` lists (msclip_amd/evalsets.py)   (zero_shot.py:208-213, 268-300)
 
 Class names and prompt templates are DATA: ImageNet's 1000 names and 80 templates (the values of the reference's
 lib/dataset/prompts/constants.py) ship as msclip_amd/data/imagenet_prompts.json; `load_prompts` reads that file, another
@@ -36,10 +38,13 @@ def prompt_name(dataset):
     return TRANSFER_NAME.get(dataset, dataset)
 
 
-def load_prompts(path="imagenet"):
+def load_prompts(path="imagenet", name="imagenet"):
     """-> (classnames, templates).  `path`: a dataset name with packaged prompts ("imagenet", as config.DATASET.DATASET
-    selects them in zero_shot.py:235-243), a json {"classes": [...], "templates": [...]} or a python constants file
-    defining IMAGENET_CLASSES / IMAGENET_DEFAULT_TEMPLATES (the reference's constants.py layout)."""
+    selects them in zero_shot.py:235-243), a json or a python constants file.  `name` picks a dataset's entry out of a file that
+    holds several: {"<name>": {"classes": [...], "templates": [...]}} in a json, ALL_CLASSES_DICT[name] / ALL_TEMPLATES_DICT[name]
+    in a constants file (the reference's constants.py layout).  A file without such an entry is read as before: a json
+    {"classes": [...], "templates": [...]}, or, for "imagenet", IMAGENET_CLASSES / IMAGENET_DEFAULT_TEMPLATES.  Only ImageNet's
+    prompts are packaged (the reference's release carries no others)."""
     if path in PROMPTS:
         path = PROMPTS[path]
     elif not os.path.exists(path):
@@ -47,10 +52,19 @@ def load_prompts(path="imagenet"):
     if path.endswith(".json"):
         with open(path) as f:
             d = json.load(f)
+        if isinstance(d.get(name), dict):
+            d = d[name]
+        elif "classes" not in d:
+            raise ValueError("Can not find prompt for dataset: {}".format(name))
         return list(d["classes"]), list(d["templates"])
     ns = runpy.run_path(path)
-    classes = ns.get("IMAGENET_CLASSES") or ns["ALL_CLASSES_DICT"]["imagenet"]
-    templates = ns.get("IMAGENET_DEFAULT_TEMPLATES") or ns["ALL_TEMPLATES_DICT"]["imagenet"]
+    if name == "imagenet":
+        classes = ns.get("IMAGENET_CLASSES") or ns["ALL_CLASSES_DICT"]["imagenet"]
+        templates = ns.get("IMAGENET_DEFAULT_TEMPLATES") or ns["ALL_TEMPLATES_DICT"]["imagenet"]
+    elif name in ns.get("ALL_CLASSES_DICT", {}) and name in ns.get("ALL_TEMPLATES_DICT", {}):
+        classes, templates = ns["ALL_CLASSES_DICT"][name], ns["ALL_TEMPLATES_DICT"][name]
+    else:
+        raise ValueError("Can not find prompt for dataset: {}".format(name))
     return list(classes), [t if isinstance(t, str) else t("{}") for t in templates]
 
 
@@ -281,34 +295,76 @@ def image_folder(root):
     return classes, items
 
 
+METRICS = ("accuracy", "mean-per-class", "11point_mAP", "roc_auc")          # TEST.METRIC (zero_shot.py:250, 280-302)
+
+
+def _check_items(items, metric, n_classes):
+    """The labels of a reader's list against the metric and the number of class names."""
+    if not items:
+        raise ValueError("evaluate: no images")
+    multi = [isinstance(c, (list, tuple)) for _, c in items]
+    if metric == "11point_mAP":
+        if not all(multi) or any(len(c) != n_classes for _, c in items):
+            raise ValueError(f"evaluate: 11point_mAP needs a multi-hot label row of {n_classes} entries per image")
+    elif any(multi):
+        raise ValueError(f"evaluate: TEST.METRIC {metric!r} needs one class index per image, not multi-hot rows")
+    elif any(not 0 <= int(c) < n_classes for _, c in items):
+        raise ValueError(f"evaluate: a label outside [0, {n_classes}), the number of class names")
+    if metric in ("mean-per-class", "roc_auc") and n_classes < 2:
+        raise ValueError(f"evaluate: TEST.METRIC {metric!r} needs at least two classes")
+
+
 @torch.no_grad()
 def evaluate(model, tokenizer, val_root, classnames, templates, batch_size=32, device="cuda", max_images=None,
              size=224, log=print, max_classes=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, dataset="imagenet",
-             metric="accuracy", return_logits=False, workers=None, processes=None):
+             metric="accuracy", return_logits=False, workers=None, processes=None, items=None):
     """Full zero-shot run: returns dict(top1, top5, n, images_per_s).  Logs the reference's final line (zero_shot.py:304-308).
     max_classes keeps the first C class directories and class names (subset runs); max_images a strided subset.
     workers: decoding threads of the input pipeline (ImagePipeline; None = one per host core up to 64; 0 = the single-threaded
     loop of rounds 1-5: PIL + numpy on the calling thread, blocking copies -- kept for the A/B and as the definition of the
-    arithmetic)."""
+    arithmetic).
+    metric: TEST.METRIC, one of METRICS.  "accuracy" counts top-1 / top-5 hits batch by batch.  For the other three every batch's
+    logits go into one fp32 [N, C] device buffer and the metric is computed behind the last batch (msclip_amd/metrics.py: the
+    ranking counts are taken on the device, the formulas applied to those integers in float64); top1 then holds the metric in
+    percent and top5 is None.
+    items: a reader's list [(path, label)] (msclip_amd/evalsets.py) instead of the ImageFolder tree at val_root; a label is a class
+    index or, for 11point_mAP, a multi-hot row over classnames."""
     import time
     from PIL import Image
     hip.require_gpu()
-    if metric != "accuracy":
-        raise NotImplementedError(f"TEST.METRIC {metric!r}: only top-1 'accuracy' (ImageNet) is on the MS-CLIP-S eval path")
-    dirs, items = image_folder(val_root)
-    if max_classes:
-        classnames = list(classnames)[:max_classes]
-        items = [(p, c) for p, c in items if c < max_classes]
-        dirs = dirs[:max_classes]
-    if len(dirs) != len(classnames):
-        raise ValueError(f"{len(dirs)} class directories under {val_root} but {len(classnames)} class names")
+    if metric not in METRICS:
+        raise ValueError(f"TEST.METRIC {metric!r}: one of {METRICS}")
+    from_reader = items is not None
+    if from_reader:
+        if val_root is not None:
+            raise ValueError("evaluate: pass either val_root (an ImageFolder tree) or items (a reader's list), not both")
+        if max_classes:
+            raise ValueError("evaluate: max_classes selects class directories of an ImageFolder tree; it does not apply to `items`")
+        items, classnames = list(items), list(classnames)
+    else:
+        dirs, items = image_folder(val_root)
+        if max_classes:
+            classnames = list(classnames)[:max_classes]
+            items = [(p, c) for p, c in items if c < max_classes]
+            dirs = dirs[:max_classes]
+        if len(dirs) != len(classnames):
+            raise ValueError(f"{len(dirs)} class directories under {val_root} but {len(classnames)} class names")
     if max_images:
         step = max(1, len(items) // max_images)
         items = items[::step][:max_images]
+    if metric != "accuracy" or from_reader:
+        _check_items(items, metric, len(classnames))
     W = zeroshot_classifier(model, tokenizer, classnames, templates, device)
     log("=> Start to inference")
     hits1 = hits5 = n = 0
     keep = []
+    if metric != "accuracy":
+        from . import metrics
+        labels = torch.tensor([c for _, c in items])
+        buf = torch.empty(len(items), W.shape[1], dtype=torch.float32, device=W.device)      # every logit of the run
+        if metric == "mean-per-class":
+            y32 = labels.to(device=W.device, dtype=torch.int32)
+            pred = torch.empty(len(items), dtype=torch.int32, device=W.device)
 
     def serial():
         for i in range(0, len(items), batch_size):
@@ -325,6 +381,13 @@ def evaluate(model, tokenizer, val_root, classnames, templates, batch_size=32, d
     for x, y, nb in (pipe if pipe is not None else serial()):
         chunk = range(nb)
         logits = 100.0 * model.encode_image(x).float() @ W
+        if metric != "accuracy":               # no host round trip per batch: the labels are known from `items`
+            rows = buf[n:n + nb]
+            rows.copy_(logits)
+            if metric == "mean-per-class":
+                metrics.predict_rows(rows, y32[n:n + nb], pred[n:n + nb])
+            n += nb
+            continue
         if return_logits:
             keep.append(logits.float().cpu())
         a1, a5 = accuracy(logits, y, (1, min(5, logits.shape[1])))
@@ -335,16 +398,29 @@ def evaluate(model, tokenizer, val_root, classnames, templates, batch_size=32, d
     elapsed = time.perf_counter() - t_start
     if pipe is not None:
         pipe.close()
-    top1, top5 = 100.0 * hits1 / max(n, 1), 100.0 * hits5 / max(n, 1)
-    log("=> {:.1f} images/s end to end ({} images, {})".format(n / max(elapsed, 1e-9), n,
-        (f"{pipe.processes} decoding processes" if pipe.processes else f"{pipe.workers} decoding threads") + ", pinned staging, copy stream"
-        if pipe is not None else "single-threaded loader"))
+    loader = ((f"{pipe.processes} decoding processes" if pipe.processes else f"{pipe.workers} decoding threads") + ", pinned staging, copy stream"
+              if pipe is not None else "single-threaded loader")
+    if metric == "accuracy":
+        top1, top5 = 100.0 * hits1 / max(n, 1), 100.0 * hits5 / max(n, 1)
+    else:
+        t0 = time.perf_counter()
+        if metric == "11point_mAP":
+            top1 = metrics.map11_percent(metrics.average_precision_11(buf, labels)[1])
+        elif metric == "roc_auc":
+            top1 = metrics.roc_auc(buf, labels, column=1) * 100
+        else:
+            top1 = metrics.mean_per_class(pred, labels, W.shape[1]) * 100
+        top5, metric_s = None, time.perf_counter() - t0
+    log("=> {:.1f} images/s end to end ({} images, {})".format(n / max(elapsed, 1e-9), n, loader))
     log("=> {dataset}% TEST:\tError@1 {error1:.3f}%\t{metric}@1 {top1:.3f}%\t".format(
-        dataset=dataset, metric=metric, top1=top1, error1=100.0 - top1) + "accuracy@5 {:.3f}%\t({} images)".format(top5, n))
+        dataset=dataset, metric=metric, top1=top1, error1=100.0 - top1)
+        + ("accuracy@5 {:.3f}%\t".format(top5) if top5 is not None else "") + "({} images)".format(n))
     res = dict(top1=top1, top5=top5, n=n, images_per_s=n / max(elapsed, 1e-9), elapsed_s=elapsed,
                loader_stats=dict(pipe.stats) if pipe is not None else None, loader_threads=(pipe.workers if pipe.processes == 0 else 0) if pipe is not None else 0,
                loader_processes=pipe.processes if pipe is not None else 0)
+    if metric != "accuracy":
+        res["metric"], res["metric_s"] = metric, metric_s
     if return_logits:
-        res["logits"], res["classifier"] = torch.cat(keep), W.float().cpu()
+        res["logits"], res["classifier"] = (torch.cat(keep) if metric == "accuracy" else buf.cpu()), W.float().cpu()
         res["labels"] = torch.tensor([c for _, c in items])
     return res
